@@ -15,12 +15,21 @@ config[1]: the ppi_bp-shaped synthetic graph, hidden=64 (config/ppi_bp.yml hyper
 dropout 0.5).  Multi-GPU = subgraph-batch data parallelism: replicated graph, per-rank batch fixed
 ("weak"), gradient all-reduce per step (--features nodeid: bucketed, see glass_amd/dist.py).
 
-Timing: after W warm-up steps, BLOCKS of exactly K steps are timed, each bracketed by a barrier +
-torch.cuda.synchronize() on both sides and taken as the MAX over ranks; at least 25 blocks and at least
-0.25 s in all (a K = 20 block of this step is 6 ms: one block alone is at the mercy of a single host
-hiccup).  ms_per_step / value come from the MEDIAN block; min / max / blocks are printed beside it.
+Timing: after W warm-up steps, ONE block of exactly K steps is timed, bracketed by a barrier +
+torch.cuda.synchronize() on both sides and taken as the MAX over ranks; ms_per_step / value come from it.
+That is all a plain run measures: it sets up, warms up, times the K steps, writes the outputs of the last
+step when --dump-outputs DIR is given, and prints the line.
 
-The JSON line also carries
+--dump-outputs DIR: after the timed steps, what the timed step hands its caller — the loss of the last step,
+every parameter after its Adam update and every gradient it computed — as DIR/<name>.npy (float32; at most
+64 MiB in all, larger arrays replaced by a fixed seeded sample of their elements).  Inputs, weights and the
+dropout stream are seeded, so two runs with the same arguments compute on identical inputs.
+
+--full adds everything else, after the headline block (and after the dump):
+  blocks         : the repeated-block protocol — at least --min-blocks further blocks of K steps and about
+                   3 s in all; ms_per_step_median_of_blocks / ms_per_step_min / ms_per_step_max / blocks
+                   (a K = 20 block of this step is 6 ms: one block alone is at the mercy of a single host hiccup).
+and the parts below (each can be switched off with its --no-* option).  The --full line carries
   roofline       : the CSR aggregation kernel (K1) inside the step — algorithmic bytes
                    nnz*(4H+8)+N*(4H+4) per launch / its average duration.  Durations come from HIP events
                    recorded on the launch stream around every K1 launch of an instrumented pass, minus the
@@ -106,6 +115,12 @@ def parse(argv=None):
                          "shuffle, drop_last) — through impl.train.train, one epoch of exactly --steps batches per timed block")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / process-group plumbing only (no GPU work; value is null) — CPU-box smoke")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated timing blocks, K1 roofline, per-call step breakdown, HBM-bound K1 "
+                         "entries, launch-chain floor, CPU baseline, collective exposure and forecast (the --no-* options "
+                         "and --min-blocks / --cpu-steps apply to this part only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss, parameters and gradients as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -170,6 +185,40 @@ def cpu_baseline(w, ei, ew, x, pos, y, steps):
             "sample": f"{steps} steps of the same workload (oracle/glass_oracle.py, torch CPU ops, {dt:.1f} s, "
                       f"{dt / steps * 1e3:.0f} ms/step, first step {first:.1f} s)",
             "ms_per_step": dt / steps * 1e3}
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, loss):
+    """--dump-outputs: what the timed step leaves its caller after its last step — the loss, every parameter after the update
+    and every gradient of that step — as float32 <out_dir>/<name>.npy (loss, param.<name>, grad.<name>).  At most 64 MiB in
+    all: the arrays are written smallest first, each allowed an equal share of what is left of the budget; an array larger
+    than its share is replaced by its elements at a fixed seeded sample of positions (sorted; the same for every run with
+    the same shapes).  -> {file stem: elements written}."""
+    import numpy as np
+    arrays = [("loss", loss.detach().reshape(1))]
+    for name, p in sorted(model.named_parameters()):
+        arrays.append(("param." + name, p.detach()))
+        if p.grad is not None:
+            arrays.append(("grad." + name, p.grad.detach()))
+    os.makedirs(out_dir, exist_ok=True)
+    left = (DUMP_BUDGET_BYTES - 256 * len(arrays)) // 4   # float32 elements, less room for every file's .npy header
+    order = sorted(range(len(arrays)), key=lambda i: arrays[i][1].numel())
+    written = {}
+    for k, i in enumerate(order):
+        name, t = arrays[i]
+        share = left // (len(order) - k)
+        if t.numel() > share:
+            rng = np.random.Generator(np.random.PCG64(0))
+            idx = np.unique(rng.integers(0, t.numel(), size=share))
+            a = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+        else:
+            a = t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.size
+        written[name] = int(a.size)
+    return written
 
 
 # ---- device-time instrumentation -----------------------------------------------------------------------------
@@ -660,6 +709,8 @@ def eval_mode(args, w, model, xg, eig, ewg, pos_g, nnz, N, H, L, world, rank, lo
 
 def main():
     args = parse()
+    if args.dump_outputs and (args.mode != "train" or args.dry_run):
+        raise SystemExit("bench.py: --dump-outputs writes what the training step computed (--mode train, no --dry-run)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -804,33 +855,74 @@ def main():
         return t.tolist()
 
     run(args.warmup, 0)
-    # blocks of EXACTLY --steps steps, each bracketed by barrier + synchronize; the first one sizes the run (same count on
-    # every rank: it is derived from the max over ranks)
-    first = max_over_ranks([timed_block(args.warmup)])[0]
+    # the headline: ONE block of exactly --steps steps, bracketed by barrier + synchronize, max over ranks
+    dt = max_over_ranks([timed_block(args.warmup)])[0]
+    last_loss = stepper.last_loss()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, torch.tensor([last_loss], dtype=torch.float32))
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "aggregated edges/sec (GLASSConv fwd+bwd)", "value": nnz * L * args.steps * world / dt,
+            "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "timed_region_s": dt,
+            "timing": f"one block of exactly {args.steps} steps after {args.warmup} warm-up steps, bracketed by barrier + "
+                      "torch.cuda.synchronize(), max over ranks",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "shipped graph + subgraphs, random-init weights" if w.name == "density" else "synthetic",
+            "config": {"workload": f"{'the shipped density graph' if w.name == 'density' else w.name + '-shaped synthetic graph'} "
+                                   f"({BASELINE_CONFIG.get(w.name, 'not a BASELINE config')}): N={N}, nnz={nnz}, "
+                                   f"hidden={H}, layers={L}, aggr={w.aggr}, pool={w.pool}, z_ratio={w.z_ratio}, "
+                                   f"dropout={w.dropout}, batch={w.batch}x{w.sub_size} per rank, "
+                                   f"{'use_nodeid (V=N)' if args.features == 'nodeid' else 'use_deg'} features, Adam",
+                       "parallelism": f"subgraph-batch dp{world}, replicated graph, bucketed gradient all-reduce per step",
+                       "step": "MaxZOZ+fwd+loss+bwd+allreduce+Adam", "hip_graph": bool(stepper.graphed),
+                       "caller": ("reference: GLASSTest.py's own objects (buildModel constructions, torch.optim.Adam, its loss callable, "
+                                  "ZGDataloader shuffle+drop_last) through impl.train.train — one epoch (incl. its host sync, the "
+                                  "shuffle and the batch selection) per timed block") if ref_caller else
+                                 "step: bench.py calls glass_amd.step.TrainStep on pre-selected batches",
+                       "labels_in_head_launch": bool(getattr(getattr(stepper, "_labels", None), "in_head", False)),
+                       "final_loss": last_loss},
+        }
+    if not args.full:
+        # (N > 1: how the exchange ran, from what the timed steps recorded; its exposed share is timed under --full)
+        collective = stepper.collective_share() if world > 1 else None
+        if rank == 0:
+            if collective is not None:
+                collective.update(exposed_us=None, exposed_method="timed under --full")
+                out["collective"] = collective
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            import torch.distributed as td
+            td.destroy_process_group()
+        return
+
+    # ---- --full: everything else, after the headline block ----
+    # further blocks of EXACTLY --steps steps, each bracketed by barrier + synchronize; the headline block sizes the run (same
+    # count on every rank: it is derived from the max over ranks) —
     # at least --min-blocks blocks and about THREE seconds of timed region (the r04 driver run rested on 0.25 s of GPU time, the
     # r05 one on 1 s: both too short for its 1 Hz utilisation samples to see the GPU phase), at most 1 200 blocks
-    n_blocks = int(min(max(args.min_blocks, -(-3.0 // max(first, 1e-6))), 1200))
-    times = [first] + [timed_block(args.warmup + (1 + b) * args.steps) for b in range(n_blocks - 1)]
+    n_blocks = int(min(max(args.min_blocks, -(-3.0 // max(dt, 1e-6))), 1200))
+    times = [timed_block(args.warmup + (1 + b) * args.steps) for b in range(n_blocks)]
     times = sorted(max_over_ranks(times))
-    dt = times[len(times) // 2]  # the median block
-    last_loss = stepper.last_loss()
+    dt_blocks = times[len(times) // 2]  # the median block
     collective = stepper.collective_share() if world > 1 else None
     if collective is not None:
         # exposed share of the exchange = step time with it - step time without it (same blocks protocol; the ranks'
         # parameters diverge from here on, which only the timing below and the instrumented pass see)
         if stepper.graphed and not stepper.collective_in_graph:
             stepper.exchange_enabled = False
-            off = args.warmup + n_blocks * args.steps
+            off = args.warmup + (1 + n_blocks) * args.steps
             t_wo = sorted(max_over_ranks([timed_block(off + b * args.steps) for b in range(max(5, n_blocks // 3))]))
             stepper.exchange_enabled = True
-            collective["exposed_us"] = (dt - t_wo[len(t_wo) // 2]) / args.steps * 1e6
+            collective["exposed_us"] = (dt_blocks - t_wo[len(t_wo) // 2]) / args.steps * 1e6
             collective["exposed_method"] = "median block with the exchange - median block with the collectives skipped"
         else:
             collective["exposed_us"] = None
             collective["exposed_method"] = "the exchange is captured inside the step's graph: no separate timing"
         # what the model expects of this line: the exchange sits between the last gradient and Adam, so unless it overlaps the
         # backward tail (embedding-sized bucket only) all of it is exposed — predicted weak-scaling efficiency of the step
-        ms = dt / args.steps * 1e3
+        ms = dt_blocks / args.steps * 1e3
         pred = collective.get("predicted_us")
         if pred is not None:
             hidden = collective["predicted"]["small_allreduce_us"] if collective.get("small_bucket_overlaps_backward_tail") else 0.0
@@ -1011,38 +1103,21 @@ def main():
         if floor is None:
             floor = {"us": None, "reason": why}
         else:
-            floor["share_of_step"] = floor["us"] * 1e-3 / (dt / args.steps * 1e3)
+            floor["share_of_step"] = floor["us"] * 1e-3 / (dt_blocks / args.steps * 1e3)
 
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(w, ei, ew, x, pos, y, args.cpu_steps)
 
     if rank == 0:
-        out = {
-            "metric": "aggregated edges/sec (GLASSConv fwd+bwd)", "value": nnz * L * args.steps * world / dt,
-            "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "ms_per_step_min": times[0] / args.steps * 1e3,
-            "ms_per_step_max": times[-1] / args.steps * 1e3, "blocks": len(times), "timed_region_s": sum(times),
-            "timing": f"median of {len(times)} blocks of exactly {args.steps} steps, each bracketed by barrier + "
-                      "torch.cuda.synchronize(), max over ranks per block",
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "shipped graph + subgraphs, random-init weights" if w.name == "density" else "synthetic",
-            "config": {"workload": f"{'the shipped density graph' if w.name == 'density' else w.name + '-shaped synthetic graph'} "
-                                   f"({BASELINE_CONFIG.get(w.name, 'not a BASELINE config')}): N={N}, nnz={nnz}, "
-                                   f"hidden={H}, layers={L}, aggr={w.aggr}, pool={w.pool}, z_ratio={w.z_ratio}, "
-                                   f"dropout={w.dropout}, batch={w.batch}x{w.sub_size} per rank, "
-                                   f"{'use_nodeid (V=N)' if args.features == 'nodeid' else 'use_deg'} features, Adam",
-                       "parallelism": f"subgraph-batch dp{world}, replicated graph, bucketed gradient all-reduce per step",
-                       "step": "MaxZOZ+fwd+loss+bwd+allreduce+Adam", "hip_graph": bool(stepper.graphed),
-                       "caller": ("reference: GLASSTest.py's own objects (buildModel constructions, torch.optim.Adam, its loss callable, "
-                                  "ZGDataloader shuffle+drop_last) through impl.train.train — one epoch (incl. its host sync, the "
-                                  "shuffle and the batch selection) per timed block") if ref_caller else
-                                 "step: bench.py calls glass_amd.step.TrainStep on pre-selected batches",
-                       "labels_in_head_launch": bool(getattr(getattr(stepper, "_labels", None), "in_head", False)),
-                       "final_loss": last_loss},
+        out.update({
+            "ms_per_step_median_of_blocks": dt_blocks / args.steps * 1e3, "ms_per_step_min": times[0] / args.steps * 1e3,
+            "ms_per_step_max": times[-1] / args.steps * 1e3, "blocks": len(times), "blocks_timed_region_s": sum(times),
+            "blocks_timing": f"median of {len(times)} further blocks of exactly {args.steps} steps, each bracketed by barrier + "
+                             "torch.cuda.synchronize(), max over ranks per block",
             "roofline": roofline, "roofline_hbm": hbm, "step_breakdown": step_breakdown, "step_floor": floor, "cpu_baseline": cpu,
             "step_floor_us": None if floor is None else floor["us"],
-        }
+        })
         if collective is not None:
             out["collective"] = collective
         # the forecast a SCALE run is to be held against: per world size the exposed exchange time under
@@ -1056,7 +1131,7 @@ def main():
                 big0 = int(getattr(bucket, "big_start", fb.numel()) or fb.numel())
                 big = (fb.numel() - big0) * es if (getattr(bucket, "shard_optimizer", False) or world == 1) else 0
                 payload = {"small_allreduce": (big0 if big else fb.numel()) * es, "big_reduce_scatter": big, "big_all_gather": big}
-                ms1 = dt / args.steps * 1e3
+                ms1 = dt_blocks / args.steps * 1e3
                 overlaps = bool(big)
                 if world > 1 and collective is not None and collective.get("predicted_exposed_us") is not None:
                     ms1 = max(ms1 - collective["predicted_exposed_us"] * 1e-3, 1e-6)

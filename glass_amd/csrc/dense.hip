@@ -3257,6 +3257,7 @@ extern "C" int glass_dual_linear_fwd_f32(const float* xa, int64_t lda, const flo
                                          int gn_act, float p_drop, const uint64_t* rng_state, uint64_t call_id, float* xa_out,
                                          int64_t ldxo, const int64_t* xa_index, int64_t xa_rows, void* stream) {
     const CallOptions call_options(act);  // act word -> activation code + this call's options
+    GLASS_REQUIRE(act_code_ok(act), "dual_linear_fwd: bad act %d", act);
     GLASS_REQUIRE(xa && W && bias && mask && out && n_nodes > 0, "dual_linear_fwd: null pointer");
     GLASS_REQUIRE((!stats_exact || (stats && wave16_shape_ok(H) && rep_ok(stats_exact))) && (!gn_src || (gn_saved && wave16_shape_ok(H))),
                   "dual_linear_fwd: exact GraphNorm accumulators are served at hidden 64 only (glass_gn_exact_supported)");

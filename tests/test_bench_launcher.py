@@ -107,3 +107,46 @@ def test_f1_distribution_comparison_rule():
     assert not f1_table.compare([0.5] * 4, [0.9, 0.91, 0.9, 0.91])["ok"]
     ref = f1_table.reference_table("density", "use_one")
     assert ref is not None and len(ref["tst"]) == 10 and "--use_one" in ref["command"] and "--repeat 10" in ref["command"]
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    """A plain run times the steps and prints the headline only; everything else is behind --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 5 and a.warmup == 2
+    b = bench.parse(["--full", "--dump-outputs", "out"])
+    assert b.full is True and b.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_every_array_within_the_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: the loss, every parameter and every gradient as float32 <name>.npy; under a byte budget the
+    small arrays stay whole and a larger one becomes a fixed seeded sample of its elements — the same on a second call."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    import torch
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(300, 400), torch.nn.Linear(400, 3))
+    m(torch.randn(5, 300)).sum().backward()
+    names = {"loss"} | {p + "." + n for n, _ in m.named_parameters() for p in ("param", "grad")}
+
+    whole = bench.dump_outputs(str(tmp_path / "whole"), m, torch.tensor([0.25]))
+    assert set(whole) == names and {f[:-4] for f in os.listdir(tmp_path / "whole")} == names
+    assert np.load(tmp_path / "whole" / "loss.npy").tolist() == [0.25]
+    w = np.load(tmp_path / "whole" / "param.0.weight.npy")
+    assert w.dtype == np.float32 and np.array_equal(w, m[0].weight.detach().numpy())
+    assert np.array_equal(np.load(tmp_path / "whole" / "grad.1.bias.npy"), m[1].bias.grad.numpy())
+
+    budget = 1 << 18
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", budget)
+    runs = [bench.dump_outputs(str(tmp_path / d), m, torch.tensor([0.25])) for d in ("a", "b")]
+    assert runs[0] == runs[1] and set(runs[0]) == names
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= budget
+    assert runs[0]["param.1.bias"] == 3 and runs[0]["grad.0.bias"] == 400          # small arrays whole
+    assert 0 < runs[0]["param.0.weight"] < 300 * 400                                # the large ones sampled
+    for f in os.listdir(tmp_path / "a"):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    sample = np.load(tmp_path / "a" / "param.0.weight.npy")
+    assert np.isin(sample, m[0].weight.detach().numpy().reshape(-1)).all()

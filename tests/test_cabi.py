@@ -336,5 +336,7 @@ def test_library_keeps_no_mutable_state():
     # an act word with an unknown activation code under the mask is still refused; option bits alone do not make it valid
     x = np.zeros(64, dtype=np.float32)
     p = x.ctypes.data
+    # (refused before any launch: the host buffers never reach a kernel)
     assert lib.glass_dual_linear_fwd_f32(p, 64, None, 0, p, p, p, 0.9, 7 | 0x100, p, 128, p, 64, 16, 64, None, 0, None, None, 0, 0.0,
                                          None, 0, None, 0, None, 0, None) != 0
+    assert b"bad act 7" in lib.glass_last_error_string()

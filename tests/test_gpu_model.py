@@ -1487,7 +1487,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo(flags, overlapped):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GLASS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--full",
                           "--no-cpu-baseline", "--no-roofline-hbm", *flags], capture_output=True, text=True, timeout=900,
                          env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -1499,6 +1499,40 @@ def test_bench_two_ranks_share_the_gpu_over_gloo(flags, overlapped):
     c = d["collective"]
     assert c["world"] == 2 and c["small_bucket_overlaps_backward_tail"] is overlapped
     assert (c["payload_bytes"]["big_reduce_scatter"] > 0) is overlapped and c["payload_bytes"]["small_allreduce"] > 0
+
+
+def test_bench_plain_run_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` run: one timed block of exactly K steps and the headline line only
+    (none of the --full parts); --dump-outputs writes the last step's loss, parameters and gradients (float32, <= 64 MiB),
+    and a second run with the same arguments writes the same arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    lines = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                              "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert out.returncode == 0, out.stderr[-3000:]
+        js = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1, out.stdout[-2000:]
+        lines.append(json.loads(js[0]))
+    d = lines[0]
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["n_gpus"] == 1 and d["value"] > 0 and d["config"]["hip_graph"]
+    assert d["unit"] == "edges/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["ms_per_step"] - d["timed_region_s"] * 1e3 / 7) <= 1e-9 * d["ms_per_step"]
+    assert not {"roofline", "roofline_hbm", "step_breakdown", "step_floor", "cpu_baseline", "blocks"} & set(d)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "loss.npy" in files
+    assert any(f.startswith("param.") for f in files) and any(f.startswith("grad.") for f in files)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [np.float32(d["config"]["final_loss"])]
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all(), f
+        assert np.abs(a - b).max() <= 1e-4 * max(np.abs(b).max(), 1e-30), f
 
 
 def test_eval_graph_parallel_branches_match_eager_forward():

@@ -7,7 +7,7 @@ from glass_amd import synth
 n, pairs, hid, layers = (int(a) for a in sys.argv[1:5])
 synth.WORKLOADS["em_user"] = dataclasses.replace(synth.WORKLOADS["em_user"], n_node=n, n_pairs=pairs, hidden=hid, layers=layers)
 import bench
-sys.argv = ["bench.py", "--workload", "em_user", "--steps", "100", "--warmup", "10", "--min-blocks", "9", "--no-cpu-baseline", "--no-roofline-hbm", "--no-pmc"]
+sys.argv = ["bench.py", "--full", "--workload", "em_user", "--steps", "100", "--warmup", "10", "--min-blocks", "9", "--no-cpu-baseline", "--no-roofline-hbm", "--no-pmc"]
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
     bench.main()

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/$1; var=$2; v1=$3; v2=$4; kexpr=$5
 mkdir -p $out
 for v in $v1 $v2 $v1 $v2; do
-  env $var=$v python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-roofline-hbm --no-pmc > $out/bench_$v.json 2> $out/bench_$v.err
+  env $var=$v python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-roofline-hbm --no-pmc > $out/bench_$v.json 2> $out/bench_$v.err
   python - <<PY
 import json
 d=json.load(open("$out/bench_$v.json"))

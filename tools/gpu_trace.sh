@@ -5,7 +5,7 @@ out=gpurun_out/${1:-trace}
 mkdir -p $out
 GLASS_HIP_LIB=$PWD/tools/bin/libglass_trace.so python tools/dense_trace.py ppi_bp > $out/dense_trace.txt 2>&1
 cat $out/dense_trace.txt
-python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-roofline-hbm --no-pmc > $out/bench_c2.json 2> $out/bench_c2.err; echo "bench c2 rc=$?"
+python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-roofline-hbm --no-pmc > $out/bench_c2.json 2> $out/bench_c2.err; echo "bench c2 rc=$?"
 python - <<PY
 import json
 d=json.load(open("$out/bench_c2.json"))

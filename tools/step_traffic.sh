@@ -8,7 +8,7 @@ out=gpurun_out/step_traffic
 rm -rf $out; mkdir -p $out
 R=${ROUND:-r06}
 W=${1:-em_user}
-ARGS="bench.py --workload $W --steps ${STEPS:-30} --warmup ${WARM:-5} --min-blocks 1 --graph 0 --no-cpu-baseline --no-roofline-hbm --no-pmc"
+ARGS="bench.py --full --workload $W --steps ${STEPS:-30} --warmup ${WARM:-5} --min-blocks 1 --graph 0 --no-cpu-baseline --no-roofline-hbm --no-pmc"
 for ctr in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out/$ctr -- python3 $ARGS > $out/$ctr.log 2>&1
   cp $(ls $out/$ctr/*/*counter_collection.csv | head -1) $out/${ctr}_raw.csv

@@ -6,7 +6,7 @@ out=gpurun_out/tiled_pmc
 rm -rf $out; mkdir -p $out
 W=${1:-powerlaw}
 PATTERN=${PATTERN:-tiled}
-ARGS="bench.py --workload $W --steps ${STEPS:-2} --warmup 1 --min-blocks 1 --graph 0 --no-cpu-baseline --no-roofline-hbm --no-pmc"
+ARGS="bench.py --full --workload $W --steps ${STEPS:-2} --warmup 1 --min-blocks 1 --graph 0 --no-cpu-baseline --no-roofline-hbm --no-pmc"
 i=0
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD" "SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM GRBM_GUI_ACTIVE" "SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_MISC SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
   i=$((i+1))
