@@ -248,7 +248,8 @@ class ParamArena(FlatGradBucket):
         from . import _lib, ops
         for i, p in enumerate(self._packs):  # the pairs' CURRENT z_ratio (the kernels receive the live value as well)
             zr[i] = float(getattr(p[5], "z_ratio", 0.0))
-        if k == 0 and rng_state is not None and table is None and zero is None:
+        # (a pack-less model's prologue may have no launch of its own to advance the dropout stream; the head launch does)
+        if k == 0 and rng_state is not None and table is None and zero is None and head is None:
             ops.rng_advance(rng_state.device)
         # table = (W, V, class_rowptr, emb_gn module, saved[4H], table-or-None): emb_gn's statistics through the embedding
         # table ride in the (first) pack launch — glass_step_prologue_f32

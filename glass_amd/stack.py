@@ -44,6 +44,7 @@ USE_GN_EXACT_FWD = os.environ.get("GLASS_GN_EXACT_FWD", "1") != "0"  # ... for t
 # queue at the memory-side atomic units, and a ~5 us finalize launch no longer shows against the kernels around it
 GN_EXACT_MAX_ROWS = 1 << 18
 GN_EXACT_FWD_ONLY_MAX_ROWS = 1 << 14  # the forward sums alone (hidden 128, one layer): see StackProgram.forward
+GN_EXACT_READOUT_MAX_ROWS = 1 << 16  # the readout's backward sums alone (H * L <= 128): see StackProgram.forward
 USE_FUSED_TAIL = os.environ.get("GLASS_FUSED_TAIL", "1") != "0"  # A/B switch: K1 slot sums + table backward + Adam as one launch
 USE_GATHER_IN_TRANS = os.environ.get("GLASS_GATHER_IN_TRANS", "1") != "0"  # A/B switch: embedding lookup inside layer 0's trans kernel
 USE_COMB_EFF = os.environ.get("GLASS_COMB_EFF", "1") != "0"  # A/B switch: comb pair through effective per-label weights
@@ -592,7 +593,7 @@ class StackProgram:
                 acc_fwd = blocks[n_bwd:] if n_fwd else None
                 acc_ro = acc_all[(n_bwd + n_fwd) * w_h:] if w_ro else None
         elif (USE_GN_EXACT and USE_READOUT_TWO and readout is not None and keep and labels is not None and H % 4 == 0 and
-              (H * L if emb.jk else H) <= 128 and n <= (1 << 16)):
+              (H * L if emb.jk else H) <= 128 and n <= GN_EXACT_READOUT_MAX_ROWS):
             # the readout's own block alone: its backward column sums in exact accumulators, folded by the backfill launch —
             # two launches instead of three (every backfill workgroup folds n_rep * 2C sums: narrow outputs, mid-size graphs)
             acc_all = acc_ro = torch.empty(int(lib.glass_gn_exact_words(H * L if emb.jk else H)), dtype=torch.int64, device=dev)

@@ -109,3 +109,18 @@ def record_parity(config, **metrics):
             json.dump(data, f, indent=1, sort_keys=True)
     except OSError:
         pass  # a read-only checkout must not fail a parity test
+
+
+# The Python A/B switches (module, attribute, non-default value); each environment variable named in the g8 switch test sets one.
+PYTHON_SWITCHES = [
+    ("glass_amd.train", "USE_STEP", False), ("glass_amd.train", "USE_GRAPH", False), ("glass_amd.train", "USE_HEAD_LABELS", False),
+    ("glass_amd.train", "USE_EVAL_GRAPH", False), ("glass_amd.models", "USE_STACK", False), ("glass_amd.ops", "USE_FUSED_DENSE", False),
+    ("glass_amd.stack", "USE_COMB_EFF", False), ("glass_amd.stack", "USE_GN_EXACT", False), ("glass_amd.stack", "USE_READOUT", False),
+    ("glass_amd.stack", "USE_READOUT_TWO", False), ("glass_amd.stack", "USE_GN_BWD_IN_COMB", False),
+    ("glass_amd.stack", "USE_GATHER_IN_TRANS", False), ("glass_amd.stack", "USE_EMBED_TABLE", False),
+    ("glass_amd.stack", "USE_FUSED_TAIL", False), ("glass_amd.stack", "USE_FUSED_BWD", False), ("glass_amd.ops", "DENSE_F32_PRODUCTS", True)]
+
+# ... those that act inside one training pass (stack.loss_and_grads or the per-op forward / backward it falls back to): every
+# switch of PYTHON_SWITCHES outside glass_amd.train, GLASS_GN_EXACT_FWD, and GLASS_DENSE_H128 / GLASS_DENSE_H256 (ops._DENSE_OFF)
+STEP_SWITCHES = [s for s in PYTHON_SWITCHES if s[0] != "glass_amd.train"] + [
+    ("glass_amd.stack", "USE_GN_EXACT_FWD", False), ("glass_amd.ops", "_DENSE_OFF", {128}), ("glass_amd.ops", "_DENSE_OFF", {256})]

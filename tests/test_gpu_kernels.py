@@ -790,6 +790,105 @@ def test_wgrad128_comb_pair_list_tiles(N, labeled):
         ops.DENSE_F32_PRODUCTS = prev
 
 
+def _canaried_ws(N, O, I):
+    """Workspace of exactly glass_linear_wgrad_ws_bytes(N, O, I) with a NaN-filled canary region right behind it."""
+    from glass_amd import _lib
+    nbytes = int(_lib.load().glass_linear_wgrad_ws_bytes(N, O, I))
+    assert nbytes > 0 and nbytes % 4 == 0
+    buf = torch.full((nbytes // 4 + 16384, ), float("nan"), device=DEV)
+    return buf, nbytes // 4, buf[nbytes // 4:].clone().view(torch.int32)
+
+
+def _wgrad_off_dispatch_check(tag, call, buf, n_ws, canary, dW_ref, db_ref):
+    """Both product forms: dW, db against the fp64 sums, two calls bit-identical, the canary behind the workspace untouched."""
+    from glass_amd import ops
+    prev = ops.DENSE_F32_PRODUCTS
+    try:
+        for form in (False, True):
+            ops.DENSE_F32_PRODUCTS = form
+            got = [call() for _ in range(2)]
+            e_w, e_b = rel_inf(got[0][0], dW_ref), rel_inf(got[0][1], db_ref)
+            assert torch.equal(buf[n_ws:].view(torch.int32).cpu(), canary.cpu()), f"{tag}: written past the workspace (f32 form {form})"
+            assert e_w < TOL and e_b < TOL, (tag, form, e_w, e_b)
+            assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1]), (tag, form)
+            if not form:
+                record_parity(f"kernel/{tag}", dW_rel_inf=e_w, db_rel_inf=e_b)
+    finally:
+        ops.DENSE_F32_PRODUCTS = prev
+
+
+@pytest.mark.parametrize("N", [8192, 50003, 400001])
+@pytest.mark.parametrize("pair,labeled", [("trans", "few"), ("comb", "few"), ("comb", "none"), ("comb", "all")])
+def test_wgrad128_shapes_off_the_wgrad128_dispatch(N, pair, labeled):
+    """glass_dual_linear_wgrad_f32 at hidden 128 on the wgrad128 row range with the wgrad128 kernels refused by their
+    alignment predicate (trans pair: ld of X = H + 2; comb pair: ld of X2 = H + 2): wgrad_geom still sizes the slabs, the
+    generic or split kernel runs on them.  dW, db against the fp64 sums in both product forms, bitwise repeat, and nothing
+    written past glass_linear_wgrad_ws_bytes."""
+    from glass_amd import ops, _lib
+    lib = _lib.load()
+    H = 128
+    gen = torch.Generator().manual_seed(N + 3 * len(labeled) + len(pair))
+    zr = 0.8
+    dsrc = torch.randn(N, H, generator=gen)
+    X = torch.randn(N, H + 2, generator=gen) if pair == "trans" else torch.randn(N, H, generator=gen)
+    X2 = torch.randn(N, H + 2, generator=gen) if pair == "comb" else None
+    T = torch.randn(N, 2 * H, generator=gen) if pair == "trans" else None
+    mask = {"few": torch.rand(N, generator=gen) < 0.02, "none": torch.zeros(N, dtype=torch.bool),
+            "all": torch.ones(N, dtype=torch.bool)}[labeled]
+    if labeled == "few":
+        mask[-1] = True
+    act = 1 if pair == "trans" else 0
+    c1 = torch.where(mask, zr, 1 - zr).double().reshape(-1, 1)
+    G = torch.cat((c1 * dsrc.double(), (1 - c1) * dsrc.double()), 1)
+    if act:
+        G = G * torch.where(T > 0, torch.ones(()), torch.exp(T)).double()
+    Xin = X[:, :H].double() if X2 is None else torch.cat((X, X2[:, :H]), 1).double()
+    dW_ref, db_ref = G.t() @ Xin, G.sum(0)
+    I = Xin.shape[1]
+    dg, Xg, mg = dsrc.to(DEV), X.to(DEV), mask.to(DEV).to(torch.uint8)
+    Tg = T.to(DEV) if act else None
+    X2g = X2.to(DEV) if X2 is not None else None
+    assert (Xg.stride(0) if X2g is None else X2g.stride(0)) % 4 == 2
+    buf, n_ws, canary = _canaried_ws(N, 2 * H, I)
+
+    def call():
+        dW = torch.full((2 * H, I), float("nan"), device=DEV)
+        db = torch.full((2 * H, ), float("nan"), device=DEV)
+        rc = lib.glass_dual_linear_wgrad_f32(dg.data_ptr(), dg.stride(0), Tg.data_ptr() if act else 0, Tg.stride(0) if act else 0,
+                                             mg.data_ptr(), zr, ops.act_word(act), Xg.data_ptr(), Xg.stride(0),
+                                             0 if X2g is None else X2g.data_ptr(), 0 if X2g is None else X2g.stride(0), N, H,
+                                             dW.data_ptr(), dW.stride(0), db.data_ptr(), 0, buf.data_ptr(),
+                                             torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, lib.glass_last_error_string()
+        return dW.cpu(), db.cpu()
+    _wgrad_off_dispatch_check(f"wgrad128_off_dispatch_{pair}_{labeled}_N{N}", call, buf, n_ws, canary, dW_ref, db_ref)
+
+
+@pytest.mark.parametrize("N", [8192, 100031])
+def test_linear_wgrad_on_wgrad128_geometry(N):
+    """glass_linear_wgrad_f32 with O = 256, I = 128 (the trans pair's shape, which wgrad_geom gives the wgrad128 slab geometry)
+    runs the generic kernel on that geometry: dW, db against the fp64 sums, bitwise repeat, nothing written past
+    glass_linear_wgrad_ws_bytes."""
+    from glass_amd import _lib
+    lib = _lib.load()
+    O_, I = 256, 128
+    gen = torch.Generator().manual_seed(N + 11)
+    G = torch.randn(N, O_, generator=gen)
+    X = torch.randn(N, I, generator=gen)
+    dW_ref, db_ref = G.double().t() @ X.double(), G.double().sum(0)
+    Gg, Xg = G.to(DEV), X.to(DEV)
+    buf, n_ws, canary = _canaried_ws(N, O_, I)
+
+    def call():
+        dW = torch.full((O_, I), float("nan"), device=DEV)
+        db = torch.full((O_, ), float("nan"), device=DEV)
+        rc = lib.glass_linear_wgrad_f32(Gg.data_ptr(), Gg.stride(0), Xg.data_ptr(), Xg.stride(0), N, O_, I, dW.data_ptr(),
+                                        dW.stride(0), db.data_ptr(), 0, buf.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, lib.glass_last_error_string()
+        return dW.cpu(), db.cpu()
+    _wgrad_off_dispatch_check(f"linear_wgrad_O256_I128_N{N}", call, buf, n_ws, canary, dW_ref, db_ref)
+
+
 @pytest.mark.parametrize("H,N,comb", [(128, 3001, False), (256, 4099, False), (256, 4099, True), (256, 70001, True),
                                       # hidden 64 (round 6: the staged forward kernels take the split form too)
                                       (64, 3001, False), (64, 17080, False), (64, 3001, True)])

@@ -741,6 +741,23 @@ def test_labels_in_the_head_launch_equal_the_eager_label_launch():
     assert torch.equal(ref, mixed)
 
 
+@pytest.mark.parametrize("hidden,switches", [(16, ()), (16, ("USE_GATHER_IN_TRANS", "USE_READOUT_TWO")), (128, ())],
+                         ids=["h16", "h16_no_table_no_acc", "h128"])
+def test_head_labels_equal_eager_labels_at_other_widths(hidden, switches, monkeypatch):
+    """The head-label form against the eager-label form (40 steps, dropout 0.5, bitwise) where the model has no packed weight
+    images (hidden 16, the narrow family) and at hidden 128.  With neither the embedding table in layer 0's launch nor
+    exact accumulators to zero-fill, hidden 16's prologue carries nothing but the dropout advance: the head launch has to
+    do that advance alone, not on top of the one the arena makes for a pack-less model."""
+    from glass_amd import stack
+    for name in switches:
+        monkeypatch.setattr(stack, name, False)
+    ref = _train_probe("tiny", hidden, 0.5, 40)
+    got, _l, cur, step = _train_probe_head("tiny", hidden, 0.5, 40)
+    assert step.graphed and step._program_step() and step._labels.in_head
+    assert cur == 40, f"cursor at {cur} after 40 replays"
+    assert torch.equal(ref, got)
+
+
 def test_step_head_labels_match_the_label_launch():
     """glass_step_head_f32 against glass_batch_labels_gather through the C ABI: two batches in a row (incremental label
     bytes), the second one with a duplicate node and a padded tail — label bytes, unique-row list and count, the copied batch

@@ -17,7 +17,7 @@ import torch.nn as nn
 from torch.nn import BCEWithLogitsLoss, CrossEntropyLoss
 from torch.optim import Adam, lr_scheduler
 
-from helpers import load, sd_from, rel_inf, flat_grads
+from helpers import load, sd_from, rel_inf, flat_grads, PYTHON_SWITCHES
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -425,12 +425,7 @@ def test_evaluation_before_the_first_training_epoch_is_not_replayed_on_stale_par
     assert abs(float(l1) - float(l0)) > 1e-3, "training did not move the loss: the check above proves nothing"
 
 
-_SWITCHES = [("glass_amd.train", "USE_STEP", False), ("glass_amd.train", "USE_GRAPH", False), ("glass_amd.train", "USE_HEAD_LABELS", False),
-             ("glass_amd.train", "USE_EVAL_GRAPH", False), ("glass_amd.models", "USE_STACK", False), ("glass_amd.ops", "USE_FUSED_DENSE", False),
-             ("glass_amd.stack", "USE_COMB_EFF", False), ("glass_amd.stack", "USE_GN_EXACT", False), ("glass_amd.stack", "USE_READOUT", False),
-             ("glass_amd.stack", "USE_READOUT_TWO", False), ("glass_amd.stack", "USE_GN_BWD_IN_COMB", False),
-             ("glass_amd.stack", "USE_GATHER_IN_TRANS", False), ("glass_amd.stack", "USE_EMBED_TABLE", False),
-             ("glass_amd.stack", "USE_FUSED_TAIL", False), ("glass_amd.stack", "USE_FUSED_BWD", False), ("glass_amd.ops", "DENSE_F32_PRODUCTS", True)]
+_SWITCHES = PYTHON_SWITCHES
 
 
 @pytest.mark.parametrize("module,name,value", _SWITCHES, ids=[f"{m.split('.')[-1]}.{n}" for m, n, _ in _SWITCHES])
