@@ -45,6 +45,17 @@ class BaseGraph:
         return torch.zeros(n, dtype=self.edge_attr.dtype).index_add_(0, self.edge_index[0].cpu(),
                                                                      self.edge_attr.cpu()).to(torch.int64)
 
+    def addDegreeFeature(self):
+        """GNN-seg: append one_hot(weighted degree) as float features (reference datasets.py:30-37) -> [N,1,maxdeg+1]."""
+        onehot = torch.nn.functional.one_hot(self._degree()).to(torch.float)
+        self.x = torch.cat((self.x.to(torch.float).cpu(), onehot.reshape(self.x.shape[0], 1, -1)),
+                           dim=-1).to(self.edge_index.device)
+
+    def addOneFeature(self):
+        """GNN-seg: append a constant 1 feature (reference datasets.py:39-43) -> [N,1,1] float."""
+        ones = torch.ones(self.x.shape[0], self.x.shape[1], 1, device=self.x.device)
+        self.x = torch.cat((self.x.to(torch.float), ones), dim=-1).to(self.edge_index.device)
+
     def setDegreeFeature(self, mod=1):
         """x[n] = rank of floor(deg(n)/mod) among the distinct values (reference datasets.py:45-52)."""
         deg = torch.div(self._degree(), mod, rounding_mode="floor")

@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("GLASS_HIP_LIB") or os.path.join(_HERE, "libglass_hip.
 
 POOL_MODES = {"sum": 0, "mean": 1, "max": 2, "size": 3}
 AGGR_MODES = {"mean": 0, "sum": 1, "gcn": 2}
+SEG_MODES = {"gcn": 0, "gin": 1}  # GLASS_SEG_GCN / GLASS_SEG_GIN
 ACT_NONE, ACT_ELU, ACT_RELU = 0, 1, 2
 PLAN_HEADER_WORDS = 16
 EMBED_NORM_MAX_ROWS = 8192  # GLASS_EMBED_NORM_MAX_ROWS
@@ -167,6 +168,10 @@ SIGNATURES = {
                                        c_uint64, c_int, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P]),
     "glass_comb_eff_bwd_gn_src_supported": (c_int, [_I, _I]),
     "glass_adam_step_f32": (c_int, [_P, _P, _P, _P, _I, _P, c_double, c_double, c_double, c_double, _P, _P]),
+    "glass_seg_extract_count": (c_int, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, c_int, _P, _P, _P, _P]),
+    "glass_seg_extract_fill": (c_int, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "glass_seg_collate": (c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I,
+                                  _P]),
 }
 
 _lib = None

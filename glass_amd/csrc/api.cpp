@@ -1,4 +1,4 @@
-// Library-wide pieces of the C ABI: version + per-thread error string.
+// Library-wide pieces of the C ABI: version + per-thread error string; host-side validation of the K10 entries.
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -20,3 +20,91 @@ void set_error(const char* fmt, ...) {
 extern "C" int glass_version(void) { return GLASS_ABI_VERSION; }
 
 extern "C" const char* glass_last_error_string(void) { return glass::g_err; }
+
+// ---- K10  GNN-seg extraction and collate: host-side validation, then the launches in seg.hip ----------------------
+namespace glass {
+int seg_extract_count_launch(const int32_t*, const int32_t*, const float*, const int32_t*, const int32_t*, const int32_t*,
+                             const int32_t*, int64_t, int, int32_t*, int32_t*, float*, void*);
+int seg_extract_fill_launch(const int32_t*, const int32_t*, const float*, const int32_t*, const int32_t*, const float*,
+                            const int32_t*, const int32_t*, int64_t, int, const float*, const int32_t*, const int32_t*,
+                            int32_t*, float*, int32_t*, float*, void*);
+int seg_collate_launch(const int32_t*, const int32_t*, int64_t, const int32_t*, const int32_t*, const float*,
+                       const int32_t*, const int32_t*, const float*, const int32_t*, int64_t, const int32_t*,
+                       const int32_t*, const int32_t*, int32_t*, float*, int32_t*, float*, int32_t*, int64_t*, int64_t,
+                       void*);
+}  // namespace glass
+
+#define SEG_REQUIRE(cond, ...)             \
+    do {                                   \
+        if (!(cond)) {                     \
+            glass::set_error(__VA_ARGS__); \
+            return GLASS_E_ARG;            \
+        }                                  \
+    } while (0)
+
+static int seg_check_inputs(const char* what, const int32_t* in_rowptr, const int32_t* in_col, const float* in_w,
+                            const int32_t* out_rowptr, const int32_t* out_col, int64_t n_base, const int32_t* sub_ptr,
+                            const int32_t* sub_nodes, int64_t n_sub, int64_t n_member, int mode) {
+    if (mode != GLASS_SEG_GCN && mode != GLASS_SEG_GIN) {
+        glass::set_error("%s: unknown mode %d (0=gcn, 1=gin)", what, mode);
+        return GLASS_E_UNSUPPORTED;
+    }
+    SEG_REQUIRE(n_base >= 0 && n_base < INT32_MAX && n_sub >= 0 && n_sub < INT32_MAX && n_member >= 0 &&
+                    n_member < INT32_MAX, "%s: negative or too large size", what);
+    SEG_REQUIRE(in_rowptr && out_rowptr && sub_ptr, "%s: null pointer", what);
+    SEG_REQUIRE(n_member == 0 || (sub_nodes && in_col && out_col), "%s: null pointer", what);
+    SEG_REQUIRE(mode != GLASS_SEG_GCN || n_member == 0 || in_w, "%s: mode gcn needs the edge weights", what);
+    return 0;
+}
+
+extern "C" int glass_seg_extract_count(const int32_t* in_rowptr, const int32_t* in_col, const float* in_w,
+                                       const int32_t* out_rowptr, const int32_t* out_col, int64_t n_base,
+                                       const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sub,
+                                       int64_t n_member, int mode, int32_t* cnt_in, int32_t* cnt_out, float* deg,
+                                       void* stream) {
+    int rc = seg_check_inputs("seg_extract_count", in_rowptr, in_col, in_w, out_rowptr, out_col, n_base, sub_ptr,
+                              sub_nodes, n_sub, n_member, mode);
+    if (rc) return rc;
+    SEG_REQUIRE(n_member == 0 || (cnt_in && cnt_out), "seg_extract_count: null count array");
+    SEG_REQUIRE(mode != GLASS_SEG_GCN || n_member == 0 || deg, "seg_extract_count: mode gcn needs deg");
+    return glass::seg_extract_count_launch(in_rowptr, in_col, in_w, out_rowptr, out_col, sub_ptr, sub_nodes, n_sub, mode,
+                                           cnt_in, cnt_out, deg, stream);
+}
+
+extern "C" int glass_seg_extract_fill(const int32_t* in_rowptr, const int32_t* in_col, const float* in_w,
+                                      const int32_t* out_rowptr, const int32_t* out_col, const float* out_w,
+                                      int64_t n_base, const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sub,
+                                      int64_t n_member, int mode, const float* deg, const int32_t* rowptr_in,
+                                      const int32_t* rowptr_out, int32_t* col_in, float* val_in, int32_t* col_out,
+                                      float* val_out, void* stream) {
+    int rc = seg_check_inputs("seg_extract_fill", in_rowptr, in_col, in_w, out_rowptr, out_col, n_base, sub_ptr,
+                              sub_nodes, n_sub, n_member, mode);
+    if (rc) return rc;
+    SEG_REQUIRE(mode != GLASS_SEG_GCN || n_member == 0 || (out_w && deg), "seg_extract_fill: mode gcn needs out_w and deg");
+    SEG_REQUIRE(n_member == 0 || (rowptr_in && rowptr_out && col_in && val_in && col_out && val_out),
+                "seg_extract_fill: null output pointer");
+    return glass::seg_extract_fill_launch(in_rowptr, in_col, in_w, out_rowptr, out_col, out_w, sub_ptr, sub_nodes, n_sub,
+                                          mode, deg, rowptr_in, rowptr_out, col_in, val_in, col_out, val_out, stream);
+}
+
+extern "C" int glass_seg_collate(const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sub,
+                                 const int32_t* rowptr_in, const int32_t* col_in, const float* val_in,
+                                 const int32_t* rowptr_out, const int32_t* col_out, const float* val_out,
+                                 const int32_t* ids, int64_t n_batch, const int32_t* node_off, int64_t n_nodes,
+                                 const int32_t* brow_in, const int32_t* brow_out, int32_t* bcol_in, float* bval_in,
+                                 int32_t* bcol_out, float* bval_out, int32_t* node_map, int64_t* pos, int64_t pos_width,
+                                 void* stream) {
+    SEG_REQUIRE(n_sub >= 0 && n_sub < INT32_MAX && n_batch >= 0 && n_batch < INT32_MAX && n_nodes >= 0 &&
+                    n_nodes < INT32_MAX && pos_width >= 0 && pos_width < INT32_MAX,
+                "seg_collate: negative or too large size");
+    if (n_batch == 0) return 0;
+    SEG_REQUIRE(sub_ptr && rowptr_in && rowptr_out && ids && node_off && brow_in && brow_out && pos,
+                "seg_collate: null pointer");
+    SEG_REQUIRE(n_nodes == 0 || (sub_nodes && node_map && col_in && val_in && col_out && val_out && bcol_in &&
+                                 bval_in && bcol_out && bval_out),
+                "seg_collate: null pointer");
+    SEG_REQUIRE(pos_width > 0 || n_nodes == 0, "seg_collate: pos_width 0 with %lld batch nodes", (long long)n_nodes);
+    return glass::seg_collate_launch(sub_ptr, sub_nodes, n_sub, rowptr_in, col_in, val_in, rowptr_out, col_out, val_out,
+                                     ids, n_batch, node_off, brow_in, brow_out, bcol_in, bval_in, bcol_out, bval_out,
+                                     node_map, pos, pos_width, stream);
+}

@@ -21,18 +21,26 @@ from . import _lib
 
 class CSROperand:
     """One CSR matrix + its K1 plan; `spmm` enqueues Y = M @ X on the current stream."""
-    def __init__(self, rowptr, col, val, n_rows, n_cols):
+    def __init__(self, rowptr, col, val, n_rows, n_cols, rowptr_host=None):
+        """rowptr_host: the same row pointer already in host memory (int32 numpy) — no device->host sync then, and the plan
+        goes up through pinned memory without waiting for the stream."""
         self.rowptr, self.col, self.val = rowptr, col, val
         self.n_rows, self.n_cols = int(n_rows), int(n_cols)
         lib = _lib.load()
-        rp_host = rowptr.cpu().numpy()  # one-time sync: the plan is host arithmetic on the row pointer
+        if rowptr_host is None:
+            rp_host = rowptr.cpu().numpy()  # one-time sync: the plan is host arithmetic on the row pointer
+        else:
+            rp_host = np.ascontiguousarray(rowptr_host, dtype=np.int32)
         words = ctypes.c_int64(0)
         _lib.check(lib.glass_spmm_plan_build(rp_host.ctypes.data, self.n_rows, None, ctypes.byref(words)), "plan size")
         plan = np.zeros(words.value, dtype=np.int32)
         _lib.check(lib.glass_spmm_plan_build(rp_host.ctypes.data, self.n_rows, plan.ctypes.data, ctypes.byref(words)),
                    "plan build")
         self.header = plan[:_lib.PLAN_HEADER_WORDS].copy()  # read on the host by every launch
-        self.plan = torch.from_numpy(plan).to(rowptr.device)
+        if rowptr_host is None:
+            self.plan = torch.from_numpy(plan).to(rowptr.device)
+        else:
+            self.plan = torch.from_numpy(plan).pin_memory().to(rowptr.device, non_blocking=True)
         self._ws = {}
 
     @property

@@ -1,0 +1,356 @@
+"""GNN-seg, the baseline the GLASS paper compares against (reference GNNSeg.py), on the HIP path.
+
+Every subgraph of a split becomes its own graph — the induced subgraph of its sorted unique node ids, hop 0
+(GNNSeg.py:213-226) — and batches are disjoint unions of those graphs (GNNSeg.py:41-62).  Here:
+
+  * `SegBase`: the base graph as CSR in both orientations (torch index plumbing, once per graph);
+  * `GsDataset`: one split, extracted by the K10 kernels (glass_seg_extract_count -> torch scan -> glass_seg_extract_fill)
+    into per-subgraph local CSR blocks, in the value mode of the model's convolution (GCN norm or GIN's A + I);
+  * `GsDataloader`: one glass_seg_collate launch per batch writes the batch's block-diagonal CSR pair, its node map and
+    its pool matrix; the row pointers and K1 plans are host arithmetic on the row lengths kept at split time (no
+    device->host sync); batches of a loader without shuffle are built once and reused;
+  * `GCNConv`, `MyGINConv`, `GConv`, `GNN`: the reference's models (PyG 1.7.2 parameter names and shapes), aggregating on
+    K1 (graph.CSROperand: target-major forward, source-major backward), GraphNorm + ELU on the GraphNorm kernels, the sum
+    pool on the segment-pool kernels.
+
+Orientation follows PyG: messages flow from edge_index[0] (source) to edge_index[1] (target), where they are summed.
+"""
+import math
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib, ops
+from .graph import CSROperand, _csr_from_sorted
+from .models import GraphNorm, _act_code
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _scan(counts):
+    rp = torch.zeros(counts.shape[0] + 1, dtype=torch.int64, device=counts.device)
+    rp[1:] = torch.cumsum(counts, 0)
+    return rp.to(torch.int32)
+
+
+class SegBase:
+    """The base graph by target (in_*: rows edge_index[1], columns sources) and by source (out_*: rows edge_index[0],
+    columns targets), (row, column)-sorted, duplicate edges kept in base order."""
+    def __init__(self, edge_index, edge_weight, n_node):
+        if not edge_index.is_cuda:
+            raise _lib.GlassHipError("GNN-seg runs on the GPU only (edge_index is on %s)" % edge_index.device)
+        n = int(n_node)
+        if n >= 2**31 - 1 or edge_index.shape[1] >= 2**31 - 1:
+            raise _lib.GlassHipError("int32 CSR: need n_node, nnz < 2^31")
+        self.n_node = n
+        src, dst = edge_index[0].to(torch.int64), edge_index[1].to(torch.int64)
+        w = edge_weight.to(device=edge_index.device, dtype=torch.float32)
+        perm = torch.argsort(dst * n + src, stable=True)
+        self.in_rowptr = _csr_from_sorted(dst[perm], n)
+        self.in_col = src[perm].to(torch.int32).contiguous()
+        self.in_w = w[perm].contiguous()
+        perm = torch.argsort(src * n + dst, stable=True)
+        self.out_rowptr = _csr_from_sorted(src[perm], n)
+        self.out_col = dst[perm].to(torch.int32).contiguous()
+        self.out_w = w[perm].contiguous()
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+class SegAdj:
+    """The normalised adjacency of one batch: fwd = target-major CSR (y[dst] = sum val * x[src]), bwd = its transpose.
+    Takes the place of edge_index in the model calls (ops.spmm reads .fwd / .bwd)."""
+    def __init__(self, fwd, bwd, mode):
+        self.fwd, self.bwd, self.mode = fwd, bwd, mode
+        self.n_node = fwd.n_rows
+
+    def edge_index(self):
+        """[2, nnz] (source, target) of the target-major entries (for checks; not on the hot path)."""
+        rp = self.fwd.rowptr.to(torch.int64)
+        dst = torch.repeat_interleave(torch.arange(self.n_node, device=rp.device), rp[1:] - rp[:-1])
+        return torch.stack((self.fwd.col.to(torch.int64), dst))
+
+
+class SegBatch:
+    """Device operands of one collated batch (the tensors the CSR operands point into are held here)."""
+    def __init__(self, ds, ids):
+        ids = np.asarray(ids, dtype=np.int64)
+        dev = ds.pos.device
+        sizes = ds.sizes_h[ids]
+        node_off = np.zeros(ids.shape[0] + 1, dtype=np.int64)
+        np.cumsum(sizes, out=node_off[1:])
+        n = int(node_off[-1])
+        rows = np.repeat(ds.sub_ptr_h[ids] - node_off[:-1], sizes) + np.arange(n, dtype=np.int64)
+        brow_in = np.zeros(n + 1, dtype=np.int64)
+        brow_out = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(ds.cnt_in_h[rows], out=brow_in[1:])
+        np.cumsum(ds.cnt_out_h[rows], out=brow_out[1:])
+        nnz_in, nnz_out = int(brow_in[-1]), int(brow_out[-1])
+        if n >= 2**31 - 1 or nnz_in >= 2**31 - 1:
+            raise _lib.GlassHipError("int32 CSR: batch too large")
+        width = max(int(sizes.max()) if sizes.size else 0, 1)
+        host = np.concatenate((ids, node_off, brow_in, brow_out)).astype(np.int32)
+        up = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+        B = ids.shape[0]
+        self.ids = up[:B].to(torch.int64)
+        node_off_d = up[B:2 * B + 1]
+        brow_in_d = up[2 * B + 1:2 * B + n + 2]
+        brow_out_d = up[2 * B + n + 2:]
+        col_in = torch.empty(nnz_in, dtype=torch.int32, device=dev)
+        val_in = torch.empty(nnz_in, dtype=torch.float32, device=dev)
+        col_out = torch.empty(nnz_out, dtype=torch.int32, device=dev)
+        val_out = torch.empty(nnz_out, dtype=torch.float32, device=dev)
+        self.node_map = torch.empty(n, dtype=torch.int32, device=dev)
+        self.pos = torch.empty((B, width), dtype=torch.int64, device=dev)
+        rc = _lib.load().glass_seg_collate(
+            ds.sub_ptr.data_ptr(), _ptr(ds.sub_nodes), ds.n_sub, ds.rowptr_in.data_ptr(), _ptr(ds.col_in), _ptr(ds.val_in),
+            ds.rowptr_out.data_ptr(), _ptr(ds.col_out), _ptr(ds.val_out), up.data_ptr(), B, node_off_d.data_ptr(), n,
+            brow_in_d.data_ptr(), brow_out_d.data_ptr(), _ptr(col_in), _ptr(val_in), _ptr(col_out), _ptr(val_out),
+            _ptr(self.node_map), self.pos.data_ptr(), width, _stream())
+        _lib.check(rc, "glass_seg_collate")
+        self.adj = SegAdj(CSROperand(brow_in_d, col_in, val_in, n, n, rowptr_host=brow_in.astype(np.int32)),
+                          CSROperand(brow_out_d, col_out, val_out, n, n, rowptr_host=brow_out.astype(np.int32)), ds.mode)
+        self.x = ds.x[self.node_map.to(torch.int64)]
+        self.y = ds.y[self.ids]
+
+    def as_tuple(self):
+        """(x [n,C,F], edge_index slot, edge_weight slot, pos, y): the reference loader's 5-tuple; the edge_index slot
+        holds the batch's SegAdj, the edge_weight slot its target-major values."""
+        return self.x, self.adj, self.adj.fwd.val, self.pos, self.y
+
+
+class GsDataset:
+    """One split of GNN-seg: every subgraph (a row of pos, -1 padding) cut out of the base graph as its induced subgraph.
+    mode: "gcn" (values of PyG's gcn_norm without self-loops) or "gin" (A + I, unit weights) — the convolution the model
+    uses.  base: a SegBase of (edge_index, edge_attr) shared by the splits of one graph (built here when None)."""
+    def __init__(self, x, edge_index, edge_attr, pos, y, mode="gcn", base=None):
+        if mode not in _lib.SEG_MODES:
+            raise NotImplementedError(f"GsDataset mode {mode!r}: gcn or gin")
+        if not pos.is_cuda:
+            raise _lib.GlassHipError("GNN-seg runs on the GPU only (pos is on %s)" % pos.device)
+        self.mode = mode
+        self.x = x if x.dtype == torch.float32 else x.to(torch.float32)
+        self.y = y
+        self.pos = pos
+        n = x.shape[0]
+        self.base = base if base is not None else SegBase(edge_index, edge_attr, n)
+        if self.base.n_node != n:
+            raise _lib.GlassHipError(f"base graph has {self.base.n_node} nodes, x has {n}")
+        # sorted unique node list of every subgraph (duplicates in a pos row merge into one node)
+        p = torch.where(pos >= 0, pos, torch.full_like(pos, n)).to(torch.int64)
+        p = torch.sort(p, dim=1).values
+        keep = p < n
+        keep[:, 1:] &= p[:, 1:] != p[:, :-1]
+        sizes = keep.sum(1)
+        self.n_sub = pos.shape[0]
+        self.sub_nodes = p[keep].to(torch.int32).contiguous()
+        self.sub_ptr = _scan(sizes)
+        self.n_member = int(self.sub_nodes.shape[0])
+        dev = pos.device
+        cnt_in = torch.empty(self.n_member, dtype=torch.int32, device=dev)
+        cnt_out = torch.empty(self.n_member, dtype=torch.int32, device=dev)
+        self.deg = torch.empty(self.n_member, dtype=torch.float32, device=dev) if mode == "gcn" else None
+        b = self.base
+        lib, m = _lib.load(), _lib.SEG_MODES[mode]
+        rc = lib.glass_seg_extract_count(b.in_rowptr.data_ptr(), _ptr(b.in_col), _ptr(b.in_w), b.out_rowptr.data_ptr(),
+                                         _ptr(b.out_col), n, self.sub_ptr.data_ptr(), _ptr(self.sub_nodes), self.n_sub,
+                                         self.n_member, m, _ptr(cnt_in), _ptr(cnt_out), _ptr(self.deg), _stream())
+        _lib.check(rc, "glass_seg_extract_count")
+        self.rowptr_in, self.rowptr_out = _scan(cnt_in), _scan(cnt_out)
+        # the split's one host sync: the row lengths every batch's row pointer and plan are built from
+        self.sizes_h = sizes.cpu().numpy().astype(np.int64)
+        self.sub_ptr_h = self.sub_ptr.cpu().numpy().astype(np.int64)
+        self.cnt_in_h = cnt_in.cpu().numpy().astype(np.int64)
+        self.cnt_out_h = cnt_out.cpu().numpy().astype(np.int64)
+        nnz_in, nnz_out = int(self.cnt_in_h.sum()), int(self.cnt_out_h.sum())
+        if nnz_in >= 2**31 - 1:
+            raise _lib.GlassHipError("int32 CSR: split too large")
+        self.col_in = torch.empty(nnz_in, dtype=torch.int32, device=dev)
+        self.val_in = torch.empty(nnz_in, dtype=torch.float32, device=dev)
+        self.col_out = torch.empty(nnz_out, dtype=torch.int32, device=dev)
+        self.val_out = torch.empty(nnz_out, dtype=torch.float32, device=dev)
+        rc = lib.glass_seg_extract_fill(b.in_rowptr.data_ptr(), _ptr(b.in_col), _ptr(b.in_w), b.out_rowptr.data_ptr(),
+                                        _ptr(b.out_col), _ptr(b.out_w), n, self.sub_ptr.data_ptr(), _ptr(self.sub_nodes),
+                                        self.n_sub, self.n_member, m, _ptr(self.deg), self.rowptr_in.data_ptr(),
+                                        self.rowptr_out.data_ptr(), _ptr(self.col_in), _ptr(self.val_in),
+                                        _ptr(self.col_out), _ptr(self.val_out), _stream())
+        _lib.check(rc, "glass_seg_extract_fill")
+
+    def __len__(self):
+        return self.n_sub
+
+    def collate(self, ids):
+        """SegBatch of the subgraphs `ids` (host integers) in that order."""
+        return SegBatch(self, ids)
+
+
+class GsDataloader:
+    """Batches of a GsDataset as (x, edge_index slot, edge_weight slot, pos, y) (GNNSeg.py:41-62).  shuffle draws a
+    permutation from torch's global generator per epoch; drop_last drops the last partial batch.  Without shuffle the
+    batches never change: they are collated once and reused."""
+    def __init__(self, Gsdataset, batch_size=64, shuffle=True, drop_last=True):
+        self.Gsdataset = Gsdataset
+        self.batch_size = int(batch_size)
+        self.shuffle, self.drop_last = shuffle, drop_last
+        self._fixed = None
+
+    def _index_batches(self):
+        n = len(self.Gsdataset)
+        order = torch.randperm(n).numpy() if self.shuffle else np.arange(n)
+        bs = self.batch_size
+        stop = (n // bs) * bs if self.drop_last else n
+        return [order[i:min(i + bs, n)] for i in range(0, stop, bs)]
+
+    def __len__(self):
+        n = len(self.Gsdataset)
+        return n // self.batch_size if self.drop_last else math.ceil(n / self.batch_size)
+
+    def __iter__(self):
+        if self.shuffle:
+            return (self.Gsdataset.collate(ids).as_tuple() for ids in self._index_batches())
+        if self._fixed is None:
+            self._fixed = [self.Gsdataset.collate(ids).as_tuple() for ids in self._index_batches()]
+        return iter(self._fixed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def _seg_adj(edge_index, mode, who):
+    if not isinstance(edge_index, SegAdj):
+        raise TypeError(f"{who} takes the SegAdj a GsDataloader yields in the edge_index slot, got {type(edge_index)}")
+    if edge_index.mode != mode:
+        raise ValueError(f"{who} needs a batch extracted in mode {mode!r} (GsDataset(mode=...)), got {edge_index.mode!r}")
+    return edge_index
+
+
+class _XW(torch.autograd.Function):
+    """x @ W with W [in, out] (PyG's layout); the weight gradient x^T @ dy on the split-K kernel where it applies."""
+    @staticmethod
+    def forward(ctx, x, W):
+        ctx.save_for_backward(x, W)
+        return x @ W
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W = ctx.saved_tensors
+        dx = dy @ W.t() if ctx.needs_input_grad[0] else None
+        dW = None
+        if ctx.needs_input_grad[1]:
+            dyc, xc = dy.contiguous(), x.contiguous()
+            dW = torch.empty_like(W, memory_format=torch.contiguous_format)
+            if not ops.linear_wgrad(xc, dyc, dW, None, accumulate=False, slot=("seg_xw", tuple(W.shape))):
+                dW = xc.t() @ dyc
+        return dx, dW
+
+
+class GCNConv(nn.Module):
+    """PyG 1.7.2 GCNConv(in, out, add_self_loops=False): out = Â (x @ weight) + bias, Â[dst, src] = dinv[src] w dinv[dst]
+    with dinv = (weighted in-degree)^-1/2 (0 where the degree is 0).  Parameters weight [in, out] (glorot), bias [out]."""
+    def __init__(self, in_channels, out_channels, add_self_loops=False, bias=True, **kwargs):
+        super().__init__()
+        if add_self_loops:
+            raise NotImplementedError("GCNConv: add_self_loops=True is not supported (GNN-seg uses False)")
+        if kwargs:
+            raise NotImplementedError(f"GCNConv: unsupported options {sorted(kwargs)}")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.weight = nn.Parameter(torch.empty(in_channels, out_channels))
+        self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        a = math.sqrt(6.0 / (self.weight.size(-2) + self.weight.size(-1)))
+        with torch.no_grad():
+            self.weight.uniform_(-a, a)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def forward(self, x, edge_index, edge_weight=None):
+        adj = _seg_adj(edge_index, "gcn", "GCNConv")
+        out = ops.spmm(adj, _XW.apply(x, self.weight))
+        return out + self.bias if self.bias is not None else out
+
+
+class _GINConv(nn.Module):
+    """PyG GINConv(nn, eps=0, train_eps=False): nn(x + sum over in-edges of x[src]); edge weights ignored."""
+    def __init__(self, mlp):
+        super().__init__()
+        self.nn = mlp
+        self.register_buffer("eps", torch.tensor([0.0]))
+
+    def forward(self, x, edge_index):
+        agg = ops.spmm(_seg_adj(edge_index, "gin", "MyGINConv"), x)  # (A + I) x: the diagonal is in the operand
+        if isinstance(self.nn, nn.Linear):
+            return ops.linear(agg, self.nn)
+        return self.nn(agg)
+
+
+class MyGINConv(nn.Module):
+    """GNNSeg.py:161-171: GINConv(nn.Linear(in, out), 0, False); reset_parameters is a no-op (torch's default init)."""
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.conv = _GINConv(nn.Linear(in_channels, out_channels))
+
+    def reset_parameters(self):
+        pass
+
+    def forward(self, x, edge_index, edge_weight=None):
+        return self.conv(x, edge_index)
+
+
+class GConv(nn.Module):
+    """num_layers convolutions in -> hidden -> ... -> out with a whole-batch GraphNorm, the activation and dropout between
+    them; returns the concatenation of every layer's output (GNNSeg.py:70-124).  With an in-place activation (the driver's
+    ELU(inplace=True)) the stored inner outputs are the ACTIVATED tensors, as in the reference."""
+    def __init__(self, input_channels, hidden_channels, output_channels, num_layers, dropout=0,
+                 activation=nn.ReLU(inplace=True), conv=GCNConv, **kwargs):
+        super().__init__()
+        dims = [input_channels] + [hidden_channels] * (num_layers - 1) + [output_channels]
+        self.convs = nn.ModuleList([conv(in_channels=dims[i], out_channels=dims[i + 1], **kwargs)
+                                    for i in range(num_layers)])
+        self.activation = activation
+        self.dropout = dropout
+        self.gns = nn.ModuleList([GraphNorm(hidden_channels) for _ in range(num_layers - 1)])
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+        for gn in self.gns:
+            gn.reset_parameters()
+
+    def forward(self, x, edge_index, edge_weight, z=None):
+        code = _act_code(self.activation)
+        inplace = bool(getattr(self.activation, "inplace", False))
+        xs = []
+        for layer, conv in enumerate(self.convs[:-1]):
+            h = conv(x, edge_index, edge_weight)
+            if inplace and code is not None:
+                h = self.gns[layer](h, act=code)  # GraphNorm + activation in one kernel: the tensor the reference stores
+                xs.append(h)
+            else:
+                pre = self.gns[layer](h)
+                h = self.activation(pre.clone() if inplace else pre)
+                xs.append(h if inplace else pre)
+            x = F.dropout(h, p=self.dropout, training=self.training)
+        xs.append(self.convs[-1](x, edge_index, edge_weight))
+        return torch.cat(xs, dim=-1) if len(xs) > 1 else xs[0]
+
+
+class GNN(nn.Module):
+    """GNNSeg.py:126-158: GConv on every feature channel x[:, c, :], mean over channels, SUM pool over each subgraph's
+    nodes (pos), then the prediction MLP.  Parameters mods.0 (GConv), mods.1 (MLP)."""
+    def __init__(self, conv, pred, aggr="sum"):
+        super().__init__()
+        self.mods = nn.ModuleList([conv, pred])
+
+    def forward(self, x, edge_index, edge_weight, subG_node, id=0):
+        C = x.shape[1]
+        embs = [self.mods[0](x[:, c, :].contiguous(), edge_index, edge_weight) for c in range(C)]
+        emb = embs[0] if C == 1 else torch.stack(embs, dim=1).mean(dim=1)
+        emb = ops.segment_pool(emb, subG_node, "sum")
+        return self.mods[1](emb)

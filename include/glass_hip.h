@@ -743,6 +743,52 @@ int glass_adam_step_f32(float* param, const float* grad, float* exp_avg, float* 
                         const float* lr_dev, double beta1, double beta2, double eps, double weight_decay,
                         int64_t* step_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K10  GNN-seg induced subgraphs and their batches (the baseline GNNSeg.py runs beside GLASS)
+ *
+ *   glass_seg_extract_count / glass_seg_extract_fill: replace GNNSeg.py:213-226 — every subgraph of a split cut out of
+ *     the base graph with k_hop_subgraph(nodes, 0, edge_index, relabel_nodes=True): its nodes are its SORTED UNIQUE
+ *     global ids, its edges every base edge with both ends among them (base order, base weight, duplicates kept).  One
+ *     workgroup per subgraph walks each member node's base rows and keeps the neighbours found by binary search in the
+ *     subgraph's list (staged in LDS when it holds <= GLASS_SEG_LDS_NODES ids, read from global memory otherwise).
+ *     Base graph: CSR by target (in_*: row = edge_index[1], columns = sources, weights) and by source (out_*: row =
+ *     edge_index[0], columns = targets, weights), both in (row, column)-sorted order.  Split: sub_ptr int32[n_sub+1],
+ *     sub_nodes int32[n_member] (n_member = sub_ptr[n_sub]; sorted unique ids per subgraph).
+ *     Output: per-subgraph local CSR blocks stacked over the split's n_member rows, columns = LOCAL ids in ascending
+ *     order, in both orientations: target-major (row = target, PyG's aggregation side) and source-major (its transpose).
+ *     count: cnt_in / cnt_out int32[n_member] entries per row; mode GCN also writes deg float[n_member] = weighted
+ *     in-degree within the subgraph.  The caller scans the counts into rowptr_in / rowptr_out int32[n_member+1].
+ *     fill: columns and values.  Mode GLASS_SEG_GCN — PyG 1.7.2 gcn_norm without self-loops:
+ *     val = dinv[src] * w * dinv[dst], dinv = deg^-1/2 with 0 for deg == 0 (no deg < 0.5 clamp).  Mode GLASS_SEG_GIN —
+ *     GINConv(eps=0): every edge 1 (weights ignored) plus one diagonal 1 per row in sorted column position (before
+ *     equal columns), so that (A + I) x is one K1 product.  Integer counts only, no float atomics: bitwise repeatable.
+ *   glass_seg_collate: replaces the PyG collate of GsDataloader (GNNSeg.py:41-62) — one launch per batch.  ids
+ *     int32[n_batch]: subgraph ids of the split in batch order; node_off int32[n_batch+1]: each block's first batch
+ *     node; brow_in / brow_out int32[n_nodes+1]: the batch row pointers (the caller builds them on the host from the
+ *     block row lengths it kept at split time).  Writes the block-diagonal batch CSR pair (columns shifted by the
+ *     block's node offset), node_map int32[n_nodes] (batch node -> global node) and pos int64[n_batch, pos_width]
+ *     (utils.batch2pad of the batch vector: the block's batch nodes, -1 padding).
+ * ---------------------------------------------------------------------------------------- */
+#define GLASS_SEG_GCN 0
+#define GLASS_SEG_GIN 1
+#define GLASS_SEG_LDS_NODES 4096
+int glass_seg_extract_count(const int32_t* in_rowptr, const int32_t* in_col, const float* in_w,
+                            const int32_t* out_rowptr, const int32_t* out_col, int64_t n_base,
+                            const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sub, int64_t n_member, int mode,
+                            int32_t* cnt_in, int32_t* cnt_out, float* deg, void* stream);
+int glass_seg_extract_fill(const int32_t* in_rowptr, const int32_t* in_col, const float* in_w,
+                           const int32_t* out_rowptr, const int32_t* out_col, const float* out_w, int64_t n_base,
+                           const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sub, int64_t n_member, int mode,
+                           const float* deg, const int32_t* rowptr_in, const int32_t* rowptr_out,
+                           int32_t* col_in, float* val_in, int32_t* col_out, float* val_out, void* stream);
+int glass_seg_collate(const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sub,
+                      const int32_t* rowptr_in, const int32_t* col_in, const float* val_in,
+                      const int32_t* rowptr_out, const int32_t* col_out, const float* val_out,
+                      const int32_t* ids, int64_t n_batch, const int32_t* node_off, int64_t n_nodes,
+                      const int32_t* brow_in, const int32_t* brow_out,
+                      int32_t* bcol_in, float* bval_in, int32_t* bcol_out, float* bval_out,
+                      int32_t* node_map, int64_t* pos, int64_t pos_width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
