@@ -3499,6 +3499,10 @@ static int dgrad_launch(const float* dsrc, int64_t ldd, const float* T, int64_t 
         GLASS_REQUIRE(wg->X && wg->ws && wg->ldx >= H && wg->ldx % 2 == 0 && (reinterpret_cast<uintptr_t>(wg->X) & 7u) == 0 &&
                           (!wg->X2 || (wg->ldx2 >= H && wg->ldx2 % 2 == 0 && (reinterpret_cast<uintptr_t>(wg->X2) & 7u) == 0)),
                       "dual_linear_bwd: the pair's inputs must be 8-B aligned with even leading dimensions");
+        // the trans pair's staged weight-gradient body builds a whole-tensor resource on X (wgrad_trans_staged2_body; with X2
+        // the comb pair's wgrad_partial_body runs instead, on 64-bit pointers)
+        GLASS_REQUIRE(wg->X2 || n_nodes * wg->ldx * 4 < (1ll << 31),
+                      "dual_linear_bwd: n_nodes * ld * 4 must stay below 2^31 (32-bit buffer offsets)");
         const WgradGeom g = wgrad_geom(n_nodes, O, I);
         float* part_w = (float*)wg->ws;
         const WgradSynth sy{dsrc, ldd, Tp, ldt, mask, zr, omz, act, (int)H, wg->X2, wg->ldx2};
@@ -3824,7 +3828,8 @@ extern "C" int glass_comb_eff_bwd_f32(const float* dsrc, int64_t ldd, const uint
 #endif
     if (GLASS_COMB_DGRAD_V2) {
         GLASS_REQUIRE(gn_act == GLASS_ACT_NONE, "comb_eff_bwd: the GraphNorm in front of the comb pair has no activation");
-        const int64_t ld_max = std::max(std::max(ldd, ldo), gn_partial ? gn_ldx : (int64_t)0);
+        // (the staged weight-gradient body builds whole-tensor resources on X and X2 too: wgrad_sl_staged2_body)
+        const int64_t ld_max = std::max(std::max(std::max(ldd, ldo), gn_partial ? gn_ldx : (int64_t)0), std::max(ldx, ldx2));
         GLASS_REQUIRE(n_nodes * ld_max * 4 < (1ll << 31), "comb_eff_bwd: n_nodes * ld * 4 must stay below 2^31 (32-bit buffer offsets)");
     }
     const size_t lds_wg = (size_t)(2 * kTile + 8 * kSLOut) * sizeof(float);

@@ -496,7 +496,7 @@ extern "C" int glass_pair_head_bwd_f32(const float* emb, int64_t lde, int64_t n_
     GLASS_REQUIRE(lde >= kPH && lde % 4 == 0 && ldde >= kPH && ldde % 4 == 0 && aligned16(emb) && aligned16(hid) && aligned16(demb) &&
                       aligned16(W0) && aligned16(w1) && aligned16(ws) && p_drop >= 0.f && p_drop < 1.f,
                   "pair_head_bwd: operands must be 16-B aligned with ld %% 4 == 0");
-    GLASS_REQUIRE(n_nodes * lde * 4 < (1ll << 31) && P * kPH * 4 < (1ll << 31) && P < (1ll << 29), "pair_head_bwd: sizes beyond the 32-bit offsets");
+    GLASS_REQUIRE(n_nodes * lde * 4 < (1ll << 31) && P * kPH * 4 < (1ll << 31) && P < (1ll << 29), "pair_head_bwd: rows * ld * 4 must stay below 2^31, P below 2^29 (32-bit buffer offsets)");
     hipStream_t st = (hipStream_t)stream;
     const int64_t n_slabs = ceil_div(P, (int64_t)kPSlabRows), n_blk = ceil_div(P, (int64_t)kPTile);
     const float inv_keep = 1.f / (1.f - p_drop);

@@ -148,16 +148,23 @@ class BatchLabels:
         self.loaded = True
 
 
-def _comb_eff_ok(conv, labels, H):
-    """forward AND backward of the comb pair in effective-weight form (hidden 64)"""
+def _comb_eff_ld(emb, H):
+    """row stride (floats) at which glass_comb_eff_max_rows caps the comb pair's rows: the widest of its operands in this
+    program — the JK output slices (H * L wide rows), the [n, 2H] data gradient — and at least 4H, the cap the effective
+    path has always been run under"""
+    return max(4 * H, H * len(emb.convs) if emb.jk else H)
+
+
+def _comb_eff_ok(conv, labels, H, ld):
+    """forward AND backward of the comb pair in effective-weight form (hidden 64); ld: _comb_eff_ld"""
     return (USE_COMB_EFF and labels is not None and getattr(conv, "_stack_eff", {}).get("comb", (None, None))[1] is not None and
-            bool(_lib.load().glass_comb_eff_supported(H)) and labels.n <= _lib.load().glass_comb_eff_max_rows(4 * H))
+            bool(_lib.load().glass_comb_eff_supported(H)) and labels.n <= _lib.load().glass_comb_eff_max_rows(ld))
 
 
-def _comb_eff_fwd_ok(conv, labels, H):
+def _comb_eff_fwd_ok(conv, labels, H, ld):
     """the forward alone (also hidden 128)"""
     return (USE_COMB_EFF and labels is not None and "comb" in getattr(conv, "_stack_eff", {}) and
-            bool(_lib.load().glass_comb_eff_fwd_supported(H)) and labels.n <= _lib.load().glass_comb_eff_max_rows(4 * H))
+            bool(_lib.load().glass_comb_eff_fwd_supported(H)) and labels.n <= _lib.load().glass_comb_eff_max_rows(ld))
 
 
 class _PendingStats:
@@ -578,7 +585,7 @@ class StackProgram:
         # about one workgroup per CU: hence the row limit)
         exact_fwd_only = (not exact_all and USE_GN_EXACT and n <= GN_EXACT_FWD_ONLY_MAX_ROWS and
                           bool(lib.glass_gn_exact_fwd_supported(H)) and L == 1 and
-                          all(_comb_eff_fwd_ok(conv, labels, H) for conv in emb.convs))
+                          all(_comb_eff_fwd_ok(conv, labels, H, _comb_eff_ld(emb, H)) for conv in emb.convs))
         if exact_all or exact_fwd_only:
             n_bwd = 2 * L - 1 if (keep and exact_all) else 0
             n_fwd = 2 * L if ((readout is not None or unl) and USE_GN_EXACT_FWD) else 0
@@ -678,7 +685,7 @@ class StackProgram:
             if unl and last:
                 cstat = None  # (nothing normalises the last layer's output: impl/models.py:469)
                 _comb_eff_fwd(a, h, conv, mask, c, None, (gsaved, ACT_NONE, pc, conv.call_base, g), labels)
-            elif _comb_eff_fwd_ok(conv, labels, H):
+            elif _comb_eff_fwd_ok(conv, labels, H, _comb_eff_ld(emb, H)):
                 cstat = acc_fwd[L + l] if acc_fwd is not None else \
                     torch.empty((int(lib.glass_comb_eff_fwd_blocks(n, H, labels.cap)), 2, H), dtype=torch.float64, device=dev)
                 _comb_eff_fwd(a, h, conv, mask, c, cstat, (gsaved, ACT_NONE, pc, conv.call_base, g), labels)
@@ -784,7 +791,7 @@ class StackProgram:
             dc_src = None
             if last:
                 dc = djk[:, l * H:(l + 1) * H] if emb.jk else djk
-            elif (USE_GN_BWD_IN_COMB and npart.dtype == torch.int64 and _comb_eff_ok(conv, st.get("labels"), H) and
+            elif (USE_GN_BWD_IN_COMB and npart.dtype == torch.int64 and _comb_eff_ok(conv, st.get("labels"), H, _comb_eff_ld(emb, H)) and
                   _lib.load().glass_comb_eff_bwd_gn_src_supported(n, H)):
                 # gns[l]'s backward apply rides in the comb launch's operand loads (glass_gn_bwd_src): no launch, no dc
                 m = emb.gns[l]
@@ -805,14 +812,14 @@ class StackProgram:
             acc_all = st.get("gn_exact")
             if acc_all is not None:
                 gpart = acc_all[2 * l]   # exact accumulators: the sums are final when the kernel is, no finalize launch
-            if acc_all is not None and _comb_eff_ok(conv, labels, H):
+            if acc_all is not None and _comb_eff_ok(conv, labels, H, _comb_eff_ld(emb, H)):
                 _comb_eff_bwd(dc, conv, mask, din, rec["g"], rec["h"], pending, acc,
                               (gpart, rec["a"], rec["gsaved"], conv.gn.mean_scale, ACT_NONE, rec["pc"], conv.call_base), labels,
                               dsrc_gn=dc_src)
             elif acc_all is not None:
                 _dual_bwd(dc, None, conv._stack["comb"], mask, conv.z_ratio, ACT_NONE, 2 * H, None, din, rec["g"], rec["h"],
                           pending, acc, gn=(gpart, rec["a"], rec["gsaved"], conv.gn.mean_scale, ACT_NONE, rec["pc"], conv.call_base))
-            elif _comb_eff_ok(conv, labels, H):
+            elif _comb_eff_ok(conv, labels, H, _comb_eff_ld(emb, H)):
                 gpart = torch.empty((int(_lib.load().glass_comb_eff_blocks(n, H, labels.cap)), 2, H), **f64)
                 _comb_eff_bwd(dc, conv, mask, din, rec["g"], rec["h"], pending, acc,
                               (gpart, rec["a"], rec["gsaved"], conv.gn.mean_scale, ACT_NONE, rec["pc"], conv.call_base), labels)
