@@ -5,7 +5,8 @@ GNNSeg.py (flags 186-194, split 213-249, buildModel 252-274, test 277-355, best 
 
 Every subgraph is cut out of the base graph as its induced subgraph and batched block-diagonally by the HIP kernels of
 glass_amd/seg.py.  Extensions: `--epochs` (default 500) caps the epochs of a repeat; `--dataset synthetic:<w>` selects
-a seeded synthetic graph (glass_amd/synth.py) run with the hyper-parameters and convolution of `<w>`.  GPU only.
+a seeded synthetic graph (glass_amd/synth.py) run with the hyper-parameters and convolution of `<w>`; `--hop K` (default
+0, the reference's value) grows every subgraph into the radius-K in-ball of its nodes (todatalist(gd, hop)).  GPU only.
 """
 import argparse
 import functools
@@ -42,6 +43,7 @@ def parse_args(argv=None):
     p.add_argument("--test", action="store_true")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--epochs", type=int, default=500, help="(extension) cap on epochs per repeat")
+    p.add_argument("--hop", type=int, default=0, help="(extension) k_hop_subgraph hops of every subgraph")
     return p.parse_args(argv)
 
 
@@ -101,7 +103,7 @@ class Run:
         self.input_channels = g.x.shape[-1]
         g.to(config.device)
         base = seg.SegBase(g.edge_index, g.edge_attr, g.x.shape[0])
-        self.trn, self.val, self.tst = (seg.GsDataset(*g.get_split(s), mode=self.mode, base=base)
+        self.trn, self.val, self.tst = (seg.GsDataset(*g.get_split(s), mode=self.mode, base=base, hop=self.args.hop)
                                         for s in ("train", "valid", "test"))
 
     def loaders(self, batch_size):

@@ -32,6 +32,8 @@ int seg_collate_launch(const int32_t*, const int32_t*, int64_t, const int32_t*, 
                        const int32_t*, const int32_t*, const float*, const int32_t*, int64_t, const int32_t*,
                        const int32_t*, const int32_t*, int32_t*, float*, int32_t*, float*, int32_t*, int64_t*, int64_t,
                        void*);
+int seg_khop_launch(const int32_t*, const int32_t*, int64_t, const int32_t*, const int32_t*, int64_t, int, void*, bool,
+                    int32_t*, const int32_t*, int32_t*, void*);
 }  // namespace glass
 
 #define SEG_REQUIRE(cond, ...)             \
@@ -107,4 +109,53 @@ extern "C" int glass_seg_collate(const int32_t* sub_ptr, const int32_t* sub_node
     return glass::seg_collate_launch(sub_ptr, sub_nodes, n_sub, rowptr_in, col_in, val_in, rowptr_out, col_out, val_out,
                                      ids, n_batch, node_off, brow_in, brow_out, bcol_in, bval_in, bcol_out, bval_out,
                                      node_map, pos, pos_width, stream);
+}
+
+extern "C" int64_t glass_seg_khop_ws_bytes(int64_t n_base, int64_t n_sub) {
+    if (n_base < 0 || n_base >= INT32_MAX || n_sub < 0 || n_sub >= INT32_MAX) return GLASS_E_ARG;
+    if (n_base <= GLASS_SEG_KHOP_LDS_NODES || n_sub == 0) return 0;
+    const int64_t slots = n_sub < GLASS_SEG_KHOP_WS_SLOTS ? n_sub : GLASS_SEG_KHOP_WS_SLOTS;
+    return slots * 3 * ((n_base + 31) / 32) * (int64_t)sizeof(uint32_t);
+}
+
+static int seg_khop_check(const char* what, const int32_t* in_rowptr, const int32_t* in_col, int64_t n_base,
+                          const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sub, int64_t n_member, int hops,
+                          const void* ws, int64_t ws_bytes) {
+    SEG_REQUIRE(n_base >= 0 && n_base < INT32_MAX && n_sub >= 0 && n_sub < INT32_MAX && n_member >= 0 &&
+                    n_member < INT32_MAX, "%s: negative or too large size (n_base, n_sub, n_member < 2^31 - 1)", what);
+    SEG_REQUIRE(hops >= 0, "%s: hops %d < 0", what, hops);
+    SEG_REQUIRE(in_rowptr && sub_ptr, "%s: null pointer", what);
+    SEG_REQUIRE(n_member == 0 || (sub_nodes && in_col), "%s: null pointer", what);
+    const int64_t need = glass_seg_khop_ws_bytes(n_base, n_sub);
+    if (need > 0 && (!ws || ws_bytes < need)) {
+        glass::set_error("%s: n_base %lld needs a workspace of %lld bytes (glass_seg_khop_ws_bytes), got %lld", what,
+                         (long long)n_base, (long long)need, ws ? (long long)ws_bytes : 0ll);
+        return GLASS_E_WS;
+    }
+    return 0;
+}
+
+extern "C" int glass_seg_khop_count(const int32_t* in_rowptr, const int32_t* in_col, int64_t n_base,
+                                    const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sub, int64_t n_member,
+                                    int hops, void* ws, int64_t ws_bytes, int32_t* ball_cnt, void* stream) {
+    int rc = seg_khop_check("seg_khop_count", in_rowptr, in_col, n_base, sub_ptr, sub_nodes, n_sub, n_member, hops, ws,
+                            ws_bytes);
+    if (rc) return rc;
+    if (n_sub == 0) return 0;
+    SEG_REQUIRE(ball_cnt, "seg_khop_count: null ball_cnt");
+    return glass::seg_khop_launch(in_rowptr, in_col, n_base, sub_ptr, sub_nodes, n_sub, hops, ws, false, ball_cnt,
+                                  nullptr, nullptr, stream);
+}
+
+extern "C" int glass_seg_khop_fill(const int32_t* in_rowptr, const int32_t* in_col, int64_t n_base,
+                                   const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sub, int64_t n_member,
+                                   int hops, void* ws, int64_t ws_bytes, const int32_t* ball_ptr, int32_t* ball_nodes,
+                                   void* stream) {
+    int rc = seg_khop_check("seg_khop_fill", in_rowptr, in_col, n_base, sub_ptr, sub_nodes, n_sub, n_member, hops, ws,
+                            ws_bytes);
+    if (rc) return rc;
+    if (n_sub == 0) return 0;
+    SEG_REQUIRE(ball_ptr && (n_member == 0 || ball_nodes), "seg_khop_fill: null output pointer");
+    return glass::seg_khop_launch(in_rowptr, in_col, n_base, sub_ptr, sub_nodes, n_sub, hops, ws, true, nullptr,
+                                  ball_ptr, ball_nodes, stream);
 }

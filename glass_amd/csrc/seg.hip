@@ -9,6 +9,11 @@
 //
 // Collate (GNNSeg.py:41-62): one workgroup per subgraph of the batch copies its block (columns shifted by the block's
 // node offset), its node map and its row of the padded pool matrix.  The batch row pointers come from the host.
+//
+// k-hop balls (GNNSeg.py:213-232, hop > 0): the node lists the extraction above takes, computed from the centre lists
+// by a breadth-first walk over bitmaps (below, at seg_khop_kernel).
+#include <algorithm>
+
 #include "common.h"
 
 namespace glass {
@@ -204,6 +209,170 @@ __global__ __launch_bounds__(kBlock) void seg_collate_kernel(const int32_t* __re
     if (m == 0) return;
     seg_copy_block(rowptr_in, col_in, val_in, r0, r0 + m, brow_in, off, off + m, off, bcol_in, bval_in);
     seg_copy_block(rowptr_out, col_out, val_out, r0, r0 + m, brow_out, off, off + m, off, bcol_out, bval_out);
+}
+
+// ---- k-hop balls (GNNSeg.py:213-232, hop > 0) ----------------------------------------------------------------------
+// One workgroup per subgraph walks in-edges breadth first over three bitmaps of the N base nodes: visited, frontier and
+// next.  They live in LDS (dynamic, 3 * ceil(N / 32) words) when N <= GLASS_SEG_KHOP_LDS_NODES, otherwise in the
+// workgroup's slice of the caller's workspace, and then the grid is capped at GLASS_SEG_KHOP_WS_SLOTS workgroups that
+// take the subgraphs in turn.  Bits are only ever set (integer atomicOr), so the ball does not depend on the order the
+// lanes run in; reading the visited words in order yields the ids ascending.
+template <bool kLds>
+struct KhopBits {
+    uint32_t* p;
+    __device__ __forceinline__ uint32_t ld(int w) const {
+        if constexpr (kLds) return p[w];
+        else return __hip_atomic_load(p + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __device__ __forceinline__ void st(int w, uint32_t v) const {
+        if constexpr (kLds) p[w] = v;
+        else __hip_atomic_store(p + w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __device__ __forceinline__ bool test(int v) const { return (ld(v >> 5) >> (v & 31)) & 1u; }
+    __device__ __forceinline__ void set(int v) const {
+        if constexpr (kLds) atomicOr(p + (v >> 5), 1u << (v & 31));
+        else __hip_atomic_fetch_or(p + (v >> 5), 1u << (v & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// Barrier between the phases of a walk; the global-memory bitmaps also get an agent-scope release / acquire around it.
+template <bool kLds>
+__device__ __forceinline__ int khop_sync_or(int pred) {
+    if constexpr (!kLds) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    const int any = __syncthreads_or(pred);
+    if constexpr (!kLds) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    return any;
+}
+
+// Leaves vis = the radius-`hops` in-ball of the subgraph's centres: each hop adds the sources of the in-edges of the
+// frontier's nodes; the walk stops early once a hop adds nothing.
+template <bool kLds>
+__device__ void khop_walk(const int32_t* in_rowptr, const int32_t* in_col, int n, int W, const int32_t* centres, int m,
+                          int hops, KhopBits<kLds> vis, KhopBits<kLds> fr, KhopBits<kLds> nx) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    for (int w = threadIdx.x; w < W; w += kBlock) {
+        vis.st(w, 0u);
+        fr.st(w, 0u);
+        nx.st(w, 0u);
+    }
+    khop_sync_or<kLds>(0);
+    for (int j = threadIdx.x; j < m; j += kBlock) {
+        const int v = centres[j];
+        if ((unsigned)v < (unsigned)n) {
+            vis.set(v);
+            fr.set(v);
+        }
+    }
+    khop_sync_or<kLds>(0);
+    for (int h = 0; h < hops; ++h) {
+        // expand: each wave reads 64 frontier words, then walks the set bits' rows together, one edge per lane
+        for (int w0 = wave * kWave; w0 < W; w0 += kBlock) {
+            const int w = w0 + lane;
+            const uint32_t f = w < W ? fr.ld(w) : 0u;
+            uint64_t nz = __ballot(f != 0u);
+            while (nz) {
+                const int l = __builtin_ctzll(nz);
+                nz &= nz - 1;
+                uint32_t fw = (uint32_t)__shfl((int)f, l, kWave);
+                while (fw) {
+                    const int u = ((w0 + l) << 5) + __builtin_ctz(fw);
+                    fw &= fw - 1;
+                    const int e1 = in_rowptr[u + 1];
+                    for (int e = in_rowptr[u] + lane; e < e1; e += kWave) {
+                        const int v = in_col[e];
+                        if ((unsigned)v < (unsigned)n && !vis.test(v)) nx.set(v);
+                    }
+                }
+            }
+        }
+        khop_sync_or<kLds>(0);
+        // update: next = next & ~visited becomes the frontier, visited |= it
+        int grew = 0;
+        for (int w = threadIdx.x; w < W; w += kBlock) {
+            const uint32_t old = vis.ld(w), x = nx.ld(w) & ~old;
+            if (x) {
+                vis.st(w, old | x);
+                grew = 1;
+            }
+            fr.st(w, x);
+            nx.st(w, 0u);
+        }
+        if (!khop_sync_or<kLds>(grew)) break;
+    }
+}
+
+// Reads vis in order: returns the ball size (the same in every thread); kFill also writes the ids ascending to out[0,
+// room).  A block-wide exclusive scan of the words' bit counts per 256-word tile (integer: bitwise repeatable).
+template <bool kLds, bool kFill>
+__device__ int khop_emit(KhopBits<kLds> vis, int W, int32_t* out, int room, int* wave_tot) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    int run = 0;
+    for (int w0 = 0; w0 < W; w0 += kBlock) {
+        const int w = w0 + threadIdx.x;
+        uint32_t bits = w < W ? vis.ld(w) : 0u;
+        const int c = __popc(bits);
+        int incl = c;
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            const int t = __shfl_up(incl, o, kWave);
+            if (lane >= o) incl += t;
+        }
+        if (lane == kWave - 1) wave_tot[wave] = incl;
+        __syncthreads();
+        int at = run + incl - c, tile = 0;
+        for (int k = 0; k < kBlock / kWave; ++k) {
+            if (k < wave) at += wave_tot[k];
+            tile += wave_tot[k];
+        }
+        if constexpr (kFill) {
+            for (; bits; bits &= bits - 1, ++at)
+                if (at < room) out[at] = (w << 5) + __builtin_ctz(bits);
+        }
+        run += tile;
+        __syncthreads();
+    }
+    return run;
+}
+
+template <bool kLds, bool kFill>
+__global__ __launch_bounds__(kBlock) void seg_khop_kernel(const int32_t* __restrict__ in_rowptr,
+                                                          const int32_t* __restrict__ in_col, int n,
+                                                          const int32_t* __restrict__ sub_ptr,
+                                                          const int32_t* __restrict__ sub_nodes, int n_sub, int hops,
+                                                          uint32_t* __restrict__ ws, int32_t* __restrict__ ball_cnt,
+                                                          const int32_t* __restrict__ ball_ptr,
+                                                          int32_t* __restrict__ ball_nodes) {
+    extern __shared__ uint32_t khop_lds[];
+    __shared__ int wave_tot[kBlock / kWave];
+    const int W = (n + 31) >> 5;
+    uint32_t* bits = kLds ? khop_lds : ws + (size_t)blockIdx.x * 3 * W;
+    const KhopBits<kLds> vis{bits}, fr{bits + W}, nx{bits + 2 * (size_t)W};
+    for (int s = blockIdx.x; s < n_sub; s += gridDim.x) {
+        const int base = sub_ptr[s];
+        khop_walk<kLds>(in_rowptr, in_col, n, W, sub_nodes + base, sub_ptr[s + 1] - base, hops, vis, fr, nx);
+        if constexpr (kFill) {
+            const int out0 = ball_ptr[s];
+            khop_emit<kLds, true>(vis, W, ball_nodes + out0, ball_ptr[s + 1] - out0, wave_tot);
+        } else {
+            const int size = khop_emit<kLds, false>(vis, W, nullptr, 0, wave_tot);
+            if (threadIdx.x == 0) ball_cnt[s] = size;
+        }
+        khop_sync_or<kLds>(0);  // (the next subgraph clears the bitmaps)
+    }
+}
+
+int seg_khop_launch(const int32_t* in_rowptr, const int32_t* in_col, int64_t n_base, const int32_t* sub_ptr,
+                    const int32_t* sub_nodes, int64_t n_sub, int hops, void* ws, bool fill, int32_t* ball_cnt,
+                    const int32_t* ball_ptr, int32_t* ball_nodes, void* stream) {
+    if (n_sub == 0) return 0;
+    const bool lds = n_base <= GLASS_SEG_KHOP_LDS_NODES;
+    const unsigned grid = (unsigned)(lds ? n_sub : std::min<int64_t>(n_sub, GLASS_SEG_KHOP_WS_SLOTS));
+    const size_t lds_bytes = lds ? (size_t)3 * ((n_base + 31) >> 5) * sizeof(uint32_t) : 0;
+    auto kernel = lds ? (fill ? seg_khop_kernel<true, true> : seg_khop_kernel<true, false>)
+                      : (fill ? seg_khop_kernel<false, true> : seg_khop_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds_bytes, (hipStream_t)stream, in_rowptr, in_col, (int)n_base,
+                       sub_ptr, sub_nodes, (int)n_sub, hops, (uint32_t*)ws, ball_cnt, ball_ptr, ball_nodes);
+    return launch_status(fill ? "glass_seg_khop_fill" : "glass_seg_khop_count");
 }
 
 int seg_extract_count_launch(const int32_t* in_rowptr, const int32_t* in_col, const float* in_w,

@@ -1,11 +1,13 @@
 """GNN-seg, the baseline the GLASS paper compares against (reference GNNSeg.py), on the HIP path.
 
-Every subgraph of a split becomes its own graph — the induced subgraph of its sorted unique node ids, hop 0
-(GNNSeg.py:213-226) — and batches are disjoint unions of those graphs (GNNSeg.py:41-62).  Here:
+Every subgraph of a split becomes its own graph — the induced subgraph of its sorted unique node ids at hop 0
+(GNNSeg.py:213-226), or of their radius-k in-ball at hop k > 0 (GNNSeg.py:213-232) — and batches are disjoint unions of
+those graphs (GNNSeg.py:41-62).  Here:
 
   * `SegBase`: the base graph as CSR in both orientations (torch index plumbing, once per graph);
   * `GsDataset`: one split, extracted by the K10 kernels (glass_seg_extract_count -> torch scan -> glass_seg_extract_fill)
-    into per-subgraph local CSR blocks, in the value mode of the model's convolution (GCN norm or GIN's A + I);
+    into per-subgraph local CSR blocks, in the value mode of the model's convolution (GCN norm or GIN's A + I); at
+    hop > 0 the node lists are first grown into k-hop in-balls (glass_seg_khop_count -> host sum -> glass_seg_khop_fill);
   * `GsDataloader`: one glass_seg_collate launch per batch writes the batch's block-diagonal CSR pair, its node map and
     its pool matrix; the row pointers and K1 plans are host arithmetic on the row lengths kept at split time (no
     device->host sync); batches of a loader without shuffle are built once and reused;
@@ -128,10 +130,16 @@ class SegBatch:
 class GsDataset:
     """One split of GNN-seg: every subgraph (a row of pos, -1 padding) cut out of the base graph as its induced subgraph.
     mode: "gcn" (values of PyG's gcn_norm without self-loops) or "gin" (A + I, unit weights) — the convolution the model
-    uses.  base: a SegBase of (edge_index, edge_attr) shared by the splits of one graph (built here when None)."""
-    def __init__(self, x, edge_index, edge_attr, pos, y, mode="gcn", base=None):
+    uses.  base: a SegBase of (edge_index, edge_attr) shared by the splits of one graph (built here when None).
+    hop: k_hop_subgraph's num_hops (GNNSeg.py:213-232) — hop > 0 replaces each row's nodes by their radius-hop in-ball
+    (glass_seg_khop_count / _fill) before the extraction; the batch pools over every node of the ball, as the reference."""
+    def __init__(self, x, edge_index, edge_attr, pos, y, mode="gcn", base=None, hop=0):
         if mode not in _lib.SEG_MODES:
             raise NotImplementedError(f"GsDataset mode {mode!r}: gcn or gin")
+        if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or hop < 0:
+            raise ValueError(f"GsDataset hop {hop!r}: a non-negative integer")
+        if hop >= 2**31:
+            raise ValueError(f"GsDataset hop {hop}: below 2^31")
         if not pos.is_cuda:
             raise _lib.GlassHipError("GNN-seg runs on the GPU only (pos is on %s)" % pos.device)
         self.mode = mode
@@ -152,7 +160,10 @@ class GsDataset:
         self.sub_nodes = p[keep].to(torch.int32).contiguous()
         self.sub_ptr = _scan(sizes)
         self.n_member = int(self.sub_nodes.shape[0])
+        self.hop = int(hop)
         dev = pos.device
+        if self.hop > 0:
+            sizes = self._balls(n)
         cnt_in = torch.empty(self.n_member, dtype=torch.int32, device=dev)
         cnt_out = torch.empty(self.n_member, dtype=torch.int32, device=dev)
         self.deg = torch.empty(self.n_member, dtype=torch.float32, device=dev) if mode == "gcn" else None
@@ -181,6 +192,28 @@ class GsDataset:
                                         self.rowptr_out.data_ptr(), _ptr(self.col_in), _ptr(self.val_in),
                                         _ptr(self.col_out), _ptr(self.val_out), _stream())
         _lib.check(rc, "glass_seg_extract_fill")
+
+    def _balls(self, n):
+        """Replaces sub_nodes / sub_ptr (the centres) by the sorted unique in-balls of radius self.hop; returns the ball
+        sizes.  One host read of the sizes, whose int64 sum is checked before anything is allocated for the fill."""
+        b, lib, dev = self.base, _lib.load(), self.pos.device
+        ws_bytes = lib.glass_seg_khop_ws_bytes(n, self.n_sub)
+        if ws_bytes < 0:
+            _lib.check(ws_bytes, "glass_seg_khop_ws_bytes")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        args = (b.in_rowptr.data_ptr(), _ptr(b.in_col), n, self.sub_ptr.data_ptr(), _ptr(self.sub_nodes), self.n_sub,
+                self.n_member, self.hop, _ptr(ws), ws_bytes)
+        ball = torch.empty(self.n_sub, dtype=torch.int32, device=dev)
+        _lib.check(lib.glass_seg_khop_count(*args, _ptr(ball), _stream()), "glass_seg_khop_count")
+        total = int(ball.cpu().numpy().astype(np.int64).sum())
+        if total >= 2**31 - 1:
+            raise _lib.GlassHipError(f"GsDataset hop {self.hop}: the balls hold {total} nodes in all; int32 node lists "
+                                     "need fewer than 2^31 - 1")
+        ball_ptr = _scan(ball)
+        nodes = torch.empty(total, dtype=torch.int32, device=dev)
+        _lib.check(lib.glass_seg_khop_fill(*args, ball_ptr.data_ptr(), _ptr(nodes), _stream()), "glass_seg_khop_fill")
+        self.sub_ptr, self.sub_nodes, self.n_member = ball_ptr, nodes, total
+        return ball
 
     def __len__(self):
         return self.n_sub

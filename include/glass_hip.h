@@ -789,6 +789,29 @@ int glass_seg_collate(const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t 
                       int32_t* bcol_in, float* bval_in, int32_t* bcol_out, float* bval_out,
                       int32_t* node_map, int64_t* pos, int64_t pos_width, void* stream);
 
+/*   glass_seg_khop_count / glass_seg_khop_fill: the node lists of k_hop_subgraph(centre, hops, edge_index,
+ *     relabel_nodes=True) for hops > 0 (GNNSeg.py:213-232; PyG 1.7.2, flow "source_to_target"): each hop adds the
+ *     sources of the in-edges of the previous hop's nodes, so the result is the radius-`hops` in-ball of the centres,
+ *     sorted and unique.  Its induced subgraph is then cut out by glass_seg_extract_count / _fill as at hop 0.
+ *     Input: the base in-CSR (in_rowptr int32[n_base+1], in_col: rows = targets, columns = sources) and the split's
+ *     sorted unique centre lists (sub_ptr / sub_nodes as above).  count: ball_cnt int32[n_sub] = ball sizes.  The caller
+ *     scans them into ball_ptr int32[n_sub+1] (the total must stay below 2^31 - 1); fill: ball_nodes int32[ball total],
+ *     each ball's ids ascending at its offset.  One workgroup per subgraph walks in-edges over visited / frontier / next
+ *     bitmaps of the n_base nodes: in LDS for n_base <= GLASS_SEG_KHOP_LDS_NODES (ws unused, may be NULL), otherwise in
+ *     ws (glass_seg_khop_ws_bytes bytes: GLASS_SEG_KHOP_WS_SLOTS workgroups at most, 3 * ceil(n_base / 32) words each;
+ *     no contents kept between calls).  Integer atomicOr only: bitwise repeatable.  Refused before any launch: null
+ *     pointers, hops < 0, sizes outside [0, 2^31 - 1) (GLASS_E_ARG), a workspace smaller than needed (GLASS_E_WS).  An
+ *     empty split (n_sub == 0) returns 0 without a launch.  glass_seg_khop_ws_bytes: GLASS_E_ARG for bad sizes. */
+#define GLASS_SEG_KHOP_LDS_NODES 131072
+#define GLASS_SEG_KHOP_WS_SLOTS 1024
+int64_t glass_seg_khop_ws_bytes(int64_t n_base, int64_t n_sub);
+int glass_seg_khop_count(const int32_t* in_rowptr, const int32_t* in_col, int64_t n_base, const int32_t* sub_ptr,
+                         const int32_t* sub_nodes, int64_t n_sub, int64_t n_member, int hops, void* ws,
+                         int64_t ws_bytes, int32_t* ball_cnt, void* stream);
+int glass_seg_khop_fill(const int32_t* in_rowptr, const int32_t* in_col, int64_t n_base, const int32_t* sub_ptr,
+                        const int32_t* sub_nodes, int64_t n_sub, int64_t n_member, int hops, void* ws, int64_t ws_bytes,
+                        const int32_t* ball_ptr, int32_t* ball_nodes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
