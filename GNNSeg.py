@@ -6,7 +6,10 @@ GNNSeg.py (flags 186-194, split 213-249, buildModel 252-274, test 277-355, best 
 Every subgraph is cut out of the base graph as its induced subgraph and batched block-diagonally by the HIP kernels of
 glass_amd/seg.py.  Extensions: `--epochs` (default 500) caps the epochs of a repeat; `--dataset synthetic:<w>` selects
 a seeded synthetic graph (glass_amd/synth.py) run with the hyper-parameters and convolution of `<w>`; `--hop K` (default
-0, the reference's value) grows every subgraph into the radius-K in-ball of its nodes (todatalist(gd, hop)).  GPU only.
+0, the reference's value) grows every subgraph into the radius-K in-ball of its nodes (todatalist(gd, hop)); `--pool
+{ball,centre}` (default ball, the reference's readout over every node of the ball) — centre pools over the subgraph's
+own nodes only, the ones the reference marks in Data.pos, and leaves the rest of the ball as context for the message
+passing; at hop 0 the two are the same run.  GPU only.
 """
 import argparse
 import functools
@@ -44,6 +47,8 @@ def parse_args(argv=None):
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--epochs", type=int, default=500, help="(extension) cap on epochs per repeat")
     p.add_argument("--hop", type=int, default=0, help="(extension) k_hop_subgraph hops of every subgraph")
+    p.add_argument("--pool", type=str, default="ball", choices=("ball", "centre"),
+                   help="(extension) readout over the whole ball, or over the subgraph's own nodes")
     return p.parse_args(argv)
 
 
@@ -103,7 +108,8 @@ class Run:
         self.input_channels = g.x.shape[-1]
         g.to(config.device)
         base = seg.SegBase(g.edge_index, g.edge_attr, g.x.shape[0])
-        self.trn, self.val, self.tst = (seg.GsDataset(*g.get_split(s), mode=self.mode, base=base, hop=self.args.hop)
+        self.trn, self.val, self.tst = (seg.GsDataset(*g.get_split(s), mode=self.mode, base=base, hop=self.args.hop,
+                                                      pool=self.args.pool)
                                         for s in ("train", "valid", "test"))
 
     def loaders(self, batch_size):

@@ -175,6 +175,9 @@ SIGNATURES = {
     "glass_seg_khop_ws_bytes": (c_int64, [_I, _I]),
     "glass_seg_khop_count": (c_int, [_P, _P, _I, _P, _P, _I, _I, c_int, _P, _I, _P, _P]),
     "glass_seg_khop_fill": (c_int, [_P, _P, _I, _P, _P, _I, _I, c_int, _P, _I, _P, _P, _P]),
+    "glass_seg_centre_index": (c_int, [_P, _P, _I, _I, _P, _P, _I, _P, _P]),
+    "glass_seg_collate_centre": (c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P,
+                                         _P, _P, _P, _I, _P, _P]),
 }
 
 _lib = None

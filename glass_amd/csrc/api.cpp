@@ -34,6 +34,11 @@ int seg_collate_launch(const int32_t*, const int32_t*, int64_t, const int32_t*, 
                        void*);
 int seg_khop_launch(const int32_t*, const int32_t*, int64_t, const int32_t*, const int32_t*, int64_t, int, void*, bool,
                     int32_t*, const int32_t*, int32_t*, void*);
+int seg_centre_index_launch(const int32_t*, const int32_t*, int64_t, const int32_t*, const int32_t*, int32_t*, void*);
+int seg_collate_centre_launch(const int32_t*, const int32_t*, int64_t, const int32_t*, const int32_t*, const float*,
+                              const int32_t*, const int32_t*, const float*, const int32_t*, const int32_t*,
+                              const int32_t*, int64_t, const int32_t*, const int32_t*, const int32_t*, int32_t*, float*,
+                              int32_t*, float*, int32_t*, int64_t*, int64_t, uint8_t*, void*);
 }  // namespace glass
 
 #define SEG_REQUIRE(cond, ...)             \
@@ -158,4 +163,56 @@ extern "C" int glass_seg_khop_fill(const int32_t* in_rowptr, const int32_t* in_c
     SEG_REQUIRE(ball_ptr && (n_member == 0 || ball_nodes), "seg_khop_fill: null output pointer");
     return glass::seg_khop_launch(in_rowptr, in_col, n_base, sub_ptr, sub_nodes, n_sub, hops, ws, true, nullptr,
                                   ball_ptr, ball_nodes, stream);
+}
+
+extern "C" int glass_seg_centre_index(const int32_t* centre_ptr, const int32_t* centre_nodes, int64_t n_sub,
+                                      int64_t n_centre, const int32_t* ball_ptr, const int32_t* ball_nodes,
+                                      int64_t n_ball, int32_t* centre_local, void* stream) {
+    SEG_REQUIRE(n_sub >= 0 && n_sub < INT32_MAX, "seg_centre_index: n_sub %lld outside [0, 2^31 - 1)", (long long)n_sub);
+    SEG_REQUIRE(n_centre >= 0 && n_centre < INT32_MAX, "seg_centre_index: n_centre %lld outside [0, 2^31 - 1)",
+                (long long)n_centre);
+    SEG_REQUIRE(n_ball >= 0 && n_ball < INT32_MAX, "seg_centre_index: n_ball %lld outside [0, 2^31 - 1)",
+                (long long)n_ball);
+    if (n_sub == 0) return 0;
+    SEG_REQUIRE(centre_ptr, "seg_centre_index: null centre_ptr");
+    SEG_REQUIRE(ball_ptr, "seg_centre_index: null ball_ptr");
+    SEG_REQUIRE(n_centre == 0 || centre_nodes, "seg_centre_index: null centre_nodes");
+    SEG_REQUIRE(n_centre == 0 || centre_local, "seg_centre_index: null centre_local");
+    SEG_REQUIRE(n_ball == 0 || ball_nodes, "seg_centre_index: null ball_nodes");
+    return glass::seg_centre_index_launch(centre_ptr, centre_nodes, n_sub, ball_ptr, ball_nodes, centre_local, stream);
+}
+
+extern "C" int glass_seg_collate_centre(const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sub,
+                                        const int32_t* rowptr_in, const int32_t* col_in, const float* val_in,
+                                        const int32_t* rowptr_out, const int32_t* col_out, const float* val_out,
+                                        const int32_t* centre_ptr, const int32_t* centre_local, int64_t n_centre,
+                                        const int32_t* ids, int64_t n_batch, const int32_t* node_off, int64_t n_nodes,
+                                        const int32_t* brow_in, const int32_t* brow_out, int32_t* bcol_in,
+                                        float* bval_in, int32_t* bcol_out, float* bval_out, int32_t* node_map,
+                                        int64_t* pos, int64_t pos_width, uint8_t* mark, void* stream) {
+    SEG_REQUIRE(n_sub >= 0 && n_sub < INT32_MAX, "seg_collate_centre: n_sub %lld outside [0, 2^31 - 1)", (long long)n_sub);
+    SEG_REQUIRE(n_centre >= 0 && n_centre < INT32_MAX, "seg_collate_centre: n_centre %lld outside [0, 2^31 - 1)",
+                (long long)n_centre);
+    SEG_REQUIRE(n_batch >= 0 && n_batch < INT32_MAX, "seg_collate_centre: n_batch %lld outside [0, 2^31 - 1)",
+                (long long)n_batch);
+    SEG_REQUIRE(n_nodes >= 0 && n_nodes < INT32_MAX, "seg_collate_centre: n_nodes %lld outside [0, 2^31 - 1)",
+                (long long)n_nodes);
+    SEG_REQUIRE(pos_width >= 0 && pos_width < INT32_MAX, "seg_collate_centre: pos_width %lld outside [0, 2^31 - 1)",
+                (long long)pos_width);
+    if (n_batch == 0) return 0;
+    SEG_REQUIRE(sub_ptr && rowptr_in && rowptr_out, "seg_collate_centre: null split row pointer (sub_ptr, rowptr_in, rowptr_out)");
+    SEG_REQUIRE(ids && node_off && brow_in && brow_out, "seg_collate_centre: null batch index (ids, node_off, brow_in, brow_out)");
+    SEG_REQUIRE(centre_ptr, "seg_collate_centre: null centre_ptr");
+    SEG_REQUIRE(n_centre == 0 || centre_local, "seg_collate_centre: null centre_local");
+    SEG_REQUIRE(pos, "seg_collate_centre: null pos");
+    SEG_REQUIRE(n_nodes == 0 || (sub_nodes && col_in && val_in && col_out && val_out),
+                "seg_collate_centre: null split array (sub_nodes, col_*, val_*)");
+    SEG_REQUIRE(n_nodes == 0 || (node_map && bcol_in && bval_in && bcol_out && bval_out),
+                "seg_collate_centre: null batch output (node_map, bcol_*, bval_*)");
+    SEG_REQUIRE(n_nodes == 0 || mark, "seg_collate_centre: null mark");
+    SEG_REQUIRE(pos_width > 0 || n_nodes == 0, "seg_collate_centre: pos_width 0 with %lld batch nodes",
+                (long long)n_nodes);
+    return glass::seg_collate_centre_launch(sub_ptr, sub_nodes, n_sub, rowptr_in, col_in, val_in, rowptr_out, col_out,
+                                            val_out, centre_ptr, centre_local, ids, n_batch, node_off, brow_in, brow_out,
+                                            bcol_in, bval_in, bcol_out, bval_out, node_map, pos, pos_width, mark, stream);
 }

@@ -12,6 +12,9 @@
 //
 // k-hop balls (GNNSeg.py:213-232, hop > 0): the node lists the extraction above takes, computed from the centre lists
 // by a breadth-first walk over bitmaps (below, at seg_khop_kernel).
+//
+// Centre marks (GNNSeg.py:214-225) and the collate that pools over the centres only: seg_centre_index_kernel and
+// seg_collate_centre_kernel, after the collate whose block body they share.
 #include <algorithm>
 
 #include "common.h"
@@ -175,6 +178,32 @@ __device__ __forceinline__ void seg_copy_block(const int32_t* rowptr, const int3
     }
 }
 
+// The part of a batch block every collate writes: its node map and its CSR pair.  Returns the block's node count (0 for
+// an id outside the split), clamped to the room the caller's node offsets leave; off = the block's first batch node.
+__device__ __forceinline__ int seg_collate_block(const int32_t* sub_ptr, const int32_t* sub_nodes, int n_sub,
+                                                 const int32_t* rowptr_in, const int32_t* col_in, const float* val_in,
+                                                 const int32_t* rowptr_out, const int32_t* col_out, const float* val_out,
+                                                 int s, const int32_t* node_off, const int32_t* brow_in,
+                                                 const int32_t* brow_out, int32_t* bcol_in, float* bval_in,
+                                                 int32_t* bcol_out, float* bval_out, int32_t* node_map, int& off) {
+    const int b = blockIdx.x;
+    off = node_off[b];
+    int m = node_off[b + 1] - off;
+    int r0 = 0;
+    if (s >= 0 && s < n_sub) {
+        r0 = sub_ptr[s];
+        const int ms = sub_ptr[s + 1] - r0;
+        if (ms < m) m = ms;
+    } else {
+        m = 0;
+    }
+    for (int j = threadIdx.x; j < m; j += kBlock) node_map[off + j] = sub_nodes[r0 + j];
+    if (m <= 0) return 0;
+    seg_copy_block(rowptr_in, col_in, val_in, r0, r0 + m, brow_in, off, off + m, off, bcol_in, bval_in);
+    seg_copy_block(rowptr_out, col_out, val_out, r0, r0 + m, brow_out, off, off + m, off, bcol_out, bval_out);
+    return m;
+}
+
 __global__ __launch_bounds__(kBlock) void seg_collate_kernel(const int32_t* __restrict__ sub_ptr,
                                                              const int32_t* __restrict__ sub_nodes, int n_sub,
                                                              const int32_t* __restrict__ rowptr_in,
@@ -191,24 +220,60 @@ __global__ __launch_bounds__(kBlock) void seg_collate_kernel(const int32_t* __re
                                                              int32_t* __restrict__ bcol_out, float* __restrict__ bval_out,
                                                              int32_t* __restrict__ node_map, int64_t* __restrict__ pos,
                                                              int pos_width) {
-    const int b = blockIdx.x;
-    const int s = ids[b];
-    const int off = node_off[b];
-    int m = node_off[b + 1] - off;
-    int r0 = 0;
-    if (s >= 0 && s < n_sub) {
-        r0 = sub_ptr[s];
-        const int ms = sub_ptr[s + 1] - r0;
-        if (ms < m) m = ms;
-    } else {
-        m = 0;
-    }
-    int64_t* prow = pos + (int64_t)b * pos_width;
+    int off;
+    const int m = seg_collate_block(sub_ptr, sub_nodes, n_sub, rowptr_in, col_in, val_in, rowptr_out, col_out, val_out,
+                                    ids[blockIdx.x], node_off, brow_in, brow_out, bcol_in, bval_in, bcol_out, bval_out,
+                                    node_map, off);
+    int64_t* prow = pos + (int64_t)blockIdx.x * pos_width;
     for (int j = threadIdx.x; j < pos_width; j += kBlock) prow[j] = j < m ? (int64_t)(off + j) : (int64_t)-1;
-    for (int j = threadIdx.x; j < m; j += kBlock) node_map[off + j] = sub_nodes[r0 + j];
-    if (m == 0) return;
-    seg_copy_block(rowptr_in, col_in, val_in, r0, r0 + m, brow_in, off, off + m, off, bcol_in, bval_in);
-    seg_copy_block(rowptr_out, col_out, val_out, r0, r0 + m, brow_out, off, off + m, off, bcol_out, bval_out);
+}
+
+// ---- centre marks of the balls (GNNSeg.py:214-225) and the collate that pools over them (GNNSeg.py:41-62) ----------
+// Position of every centre in its own ball's sorted list: one workgroup per subgraph stages the ball (LDS or global, as
+// the extraction does), one centre per lane, binary search.  -1 for a centre its ball does not hold.
+__global__ __launch_bounds__(kBlock) void seg_centre_index_kernel(const int32_t* __restrict__ centre_ptr,
+                                                                  const int32_t* __restrict__ centre_nodes,
+                                                                  const int32_t* __restrict__ ball_ptr,
+                                                                  const int32_t* __restrict__ ball_nodes,
+                                                                  int32_t* __restrict__ centre_local) {
+    __shared__ int lds[kSegLds];
+    const int base = ball_ptr[blockIdx.x], m = ball_ptr[blockIdx.x + 1] - base;
+    const int* list = seg_stage(lds, ball_nodes, base, m);
+    const int c1 = centre_ptr[blockIdx.x + 1];
+    for (int j = centre_ptr[blockIdx.x] + threadIdx.x; j < c1; j += kBlock)
+        centre_local[j] = seg_find(list, m, centre_nodes[j]);
+}
+
+// The collate of a batch that pools over the centres: the block as above; the pos row lists the batch rows of the
+// block's centres (their local indices ascend with the sorted centre ids); mark is 1 on those rows and 0 on the other
+// rows of the ball.  Each mark byte has one writer: the row looks itself up in the block's centre_local list.
+__global__ __launch_bounds__(kBlock) void seg_collate_centre_kernel(
+    const int32_t* __restrict__ sub_ptr, const int32_t* __restrict__ sub_nodes, int n_sub,
+    const int32_t* __restrict__ rowptr_in, const int32_t* __restrict__ col_in, const float* __restrict__ val_in,
+    const int32_t* __restrict__ rowptr_out, const int32_t* __restrict__ col_out, const float* __restrict__ val_out,
+    const int32_t* __restrict__ centre_ptr, const int32_t* __restrict__ centre_local, const int32_t* __restrict__ ids,
+    const int32_t* __restrict__ node_off, const int32_t* __restrict__ brow_in, const int32_t* __restrict__ brow_out,
+    int32_t* __restrict__ bcol_in, float* __restrict__ bval_in, int32_t* __restrict__ bcol_out,
+    float* __restrict__ bval_out, int32_t* __restrict__ node_map, int64_t* __restrict__ pos, int pos_width,
+    uint8_t* __restrict__ mark) {
+    const int s = ids[blockIdx.x];
+    int off;
+    const int m = seg_collate_block(sub_ptr, sub_nodes, n_sub, rowptr_in, col_in, val_in, rowptr_out, col_out, val_out,
+                                    s, node_off, brow_in, brow_out, bcol_in, bval_in, bcol_out, bval_out, node_map, off);
+    int c0 = 0, k = 0;
+    if (m > 0) {
+        c0 = centre_ptr[s];
+        k = centre_ptr[s + 1] - c0;
+    }
+    const int32_t* loc = centre_local + c0;
+    int64_t* prow = pos + (int64_t)blockIdx.x * pos_width;
+    for (int j = threadIdx.x; j < pos_width; j += kBlock) {
+        const int l = j < k ? loc[j] : -1;
+        prow[j] = (unsigned)l < (unsigned)m ? (int64_t)(off + l) : (int64_t)-1;
+    }
+    // (every row of the block's node range, also rows past a clamped m: the launch leaves no byte of mark unwritten)
+    const int room = node_off[blockIdx.x + 1] - off;
+    for (int j = threadIdx.x; j < room; j += kBlock) mark[off + j] = (j < m && seg_find(loc, k, j) >= 0) ? 1 : 0;
 }
 
 // ---- k-hop balls (GNNSeg.py:213-232, hop > 0) ----------------------------------------------------------------------
@@ -408,6 +473,29 @@ int seg_collate_launch(const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t
                        sub_nodes, (int)n_sub, rowptr_in, col_in, val_in, rowptr_out, col_out, val_out, ids, node_off,
                        brow_in, brow_out, bcol_in, bval_in, bcol_out, bval_out, node_map, pos, (int)pos_width);
     return launch_status("glass_seg_collate");
+}
+
+int seg_centre_index_launch(const int32_t* centre_ptr, const int32_t* centre_nodes, int64_t n_sub,
+                            const int32_t* ball_ptr, const int32_t* ball_nodes, int32_t* centre_local, void* stream) {
+    if (n_sub == 0) return 0;
+    hipLaunchKernelGGL(seg_centre_index_kernel, dim3((unsigned)n_sub), dim3(kBlock), 0, (hipStream_t)stream, centre_ptr,
+                       centre_nodes, ball_ptr, ball_nodes, centre_local);
+    return launch_status("glass_seg_centre_index");
+}
+
+int seg_collate_centre_launch(const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sub, const int32_t* rowptr_in,
+                              const int32_t* col_in, const float* val_in, const int32_t* rowptr_out,
+                              const int32_t* col_out, const float* val_out, const int32_t* centre_ptr,
+                              const int32_t* centre_local, const int32_t* ids, int64_t n_batch, const int32_t* node_off,
+                              const int32_t* brow_in, const int32_t* brow_out, int32_t* bcol_in, float* bval_in,
+                              int32_t* bcol_out, float* bval_out, int32_t* node_map, int64_t* pos, int64_t pos_width,
+                              uint8_t* mark, void* stream) {
+    if (n_batch == 0) return 0;
+    hipLaunchKernelGGL(seg_collate_centre_kernel, dim3((unsigned)n_batch), dim3(kBlock), 0, (hipStream_t)stream, sub_ptr,
+                       sub_nodes, (int)n_sub, rowptr_in, col_in, val_in, rowptr_out, col_out, val_out, centre_ptr,
+                       centre_local, ids, node_off, brow_in, brow_out, bcol_in, bval_in, bcol_out, bval_out, node_map, pos,
+                       (int)pos_width, mark);
+    return launch_status("glass_seg_collate_centre");
 }
 
 }  // namespace glass

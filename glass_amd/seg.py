@@ -11,6 +11,10 @@ those graphs (GNNSeg.py:41-62).  Here:
   * `GsDataloader`: one glass_seg_collate launch per batch writes the batch's block-diagonal CSR pair, its node map and
     its pool matrix; the row pointers and K1 plans are host arithmetic on the row lengths kept at split time (no
     device->host sync); batches of a loader without shuffle are built once and reused;
+  * `GsDataset(pool="centre")` at hop > 0: message passing runs over the ball, the readout over the subgraph's own nodes.
+    glass_seg_centre_index finds every centre in its ball once per split (the reference's `inv`, GNNSeg.py:214-225), and
+    glass_seg_collate_centre is then the batch's one launch: the same CSR pair and node map, a pool matrix that lists
+    only the centres' rows, and the 0/1 centre mark of every batch row (the reference's Data.pos);
   * `GCNConv`, `MyGINConv`, `GConv`, `GNN`: the reference's models (PyG 1.7.2 parameter names and shapes), aggregating on
     K1 (graph.CSROperand: target-major forward, source-major backward), GraphNorm + ELU on the GraphNorm kernels, the sum
     pool on the segment-pool kernels.
@@ -80,7 +84,11 @@ class SegAdj:
 
 
 class SegBatch:
-    """Device operands of one collated batch (the tensors the CSR operands point into are held here)."""
+    """Device operands of one collated batch (the tensors the CSR operands point into are held here).  pos lists the rows
+    the readout pools: every row of a block, or, for a GsDataset(pool="centre") at hop > 0, the rows of its centres.
+    mark (uint8 per batch row, 1 on a centre: the reference's Data.pos over the batch) is written by the centre collate;
+    at hop 0 every row is a centre and the all-ones mark is made when first read (no launch on the collate path); in
+    ball mode at hop > 0 the split never located its centres and mark is None."""
     def __init__(self, ds, ids):
         ids = np.asarray(ids, dtype=np.int64)
         dev = ds.pos.device
@@ -96,7 +104,9 @@ class SegBatch:
         nnz_in, nnz_out = int(brow_in[-1]), int(brow_out[-1])
         if n >= 2**31 - 1 or nnz_in >= 2**31 - 1:
             raise _lib.GlassHipError("int32 CSR: batch too large")
-        width = max(int(sizes.max()) if sizes.size else 0, 1)
+        centre = ds.centre_local is not None
+        pooled = ds.centre_sizes_h[ids] if centre else sizes
+        width = max(int(pooled.max()) if pooled.size else 0, 1)
         host = np.concatenate((ids, node_off, brow_in, brow_out)).astype(np.int32)
         up = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
         B = ids.shape[0]
@@ -110,16 +120,29 @@ class SegBatch:
         val_out = torch.empty(nnz_out, dtype=torch.float32, device=dev)
         self.node_map = torch.empty(n, dtype=torch.int32, device=dev)
         self.pos = torch.empty((B, width), dtype=torch.int64, device=dev)
-        rc = _lib.load().glass_seg_collate(
-            ds.sub_ptr.data_ptr(), _ptr(ds.sub_nodes), ds.n_sub, ds.rowptr_in.data_ptr(), _ptr(ds.col_in), _ptr(ds.val_in),
-            ds.rowptr_out.data_ptr(), _ptr(ds.col_out), _ptr(ds.val_out), up.data_ptr(), B, node_off_d.data_ptr(), n,
-            brow_in_d.data_ptr(), brow_out_d.data_ptr(), _ptr(col_in), _ptr(val_in), _ptr(col_out), _ptr(val_out),
-            _ptr(self.node_map), self.pos.data_ptr(), width, _stream())
-        _lib.check(rc, "glass_seg_collate")
+        split = (ds.sub_ptr.data_ptr(), _ptr(ds.sub_nodes), ds.n_sub, ds.rowptr_in.data_ptr(), _ptr(ds.col_in),
+                 _ptr(ds.val_in), ds.rowptr_out.data_ptr(), _ptr(ds.col_out), _ptr(ds.val_out))
+        batch = (up.data_ptr(), B, node_off_d.data_ptr(), n, brow_in_d.data_ptr(), brow_out_d.data_ptr(), _ptr(col_in),
+                 _ptr(val_in), _ptr(col_out), _ptr(val_out), _ptr(self.node_map), self.pos.data_ptr(), width)
+        self._all_centres = ds.hop == 0
+        if centre:
+            self._mark = torch.empty(n, dtype=torch.uint8, device=dev)
+            rc = _lib.load().glass_seg_collate_centre(*split, ds.centre_ptr.data_ptr(), _ptr(ds.centre_local),
+                                                      ds.n_centre, *batch, _ptr(self._mark), _stream())
+            _lib.check(rc, "glass_seg_collate_centre")
+        else:
+            self._mark = None
+            _lib.check(_lib.load().glass_seg_collate(*split, *batch, _stream()), "glass_seg_collate")
         self.adj = SegAdj(CSROperand(brow_in_d, col_in, val_in, n, n, rowptr_host=brow_in.astype(np.int32)),
                           CSROperand(brow_out_d, col_out, val_out, n, n, rowptr_host=brow_out.astype(np.int32)), ds.mode)
         self.x = ds.x[self.node_map.to(torch.int64)]
         self.y = ds.y[self.ids]
+
+    @property
+    def mark(self):
+        if self._mark is None and self._all_centres:
+            self._mark = torch.ones(self.node_map.shape[0], dtype=torch.uint8, device=self.node_map.device)
+        return self._mark
 
     def as_tuple(self):
         """(x [n,C,F], edge_index slot, edge_weight slot, pos, y): the reference loader's 5-tuple; the edge_index slot
@@ -132,10 +155,16 @@ class GsDataset:
     mode: "gcn" (values of PyG's gcn_norm without self-loops) or "gin" (A + I, unit weights) — the convolution the model
     uses.  base: a SegBase of (edge_index, edge_attr) shared by the splits of one graph (built here when None).
     hop: k_hop_subgraph's num_hops (GNNSeg.py:213-232) — hop > 0 replaces each row's nodes by their radius-hop in-ball
-    (glass_seg_khop_count / _fill) before the extraction; the batch pools over every node of the ball, as the reference."""
-    def __init__(self, x, edge_index, edge_attr, pos, y, mode="gcn", base=None, hop=0):
+    (glass_seg_khop_count / _fill) before the extraction.
+    pool: "ball" (the reference: the batch pools over every node of the ball) or "centre" (it pools over the subgraph's
+    own nodes only, the ones the reference marks in Data.pos, GNNSeg.py:214-225; the ball is context for the message
+    passing).  At hop 0 the two are the same batches.  The centre lists stay in centre_ptr / centre_nodes /
+    centre_sizes_h either way; centre_local (each centre's row within its ball's block) exists for "centre" at hop > 0."""
+    def __init__(self, x, edge_index, edge_attr, pos, y, mode="gcn", base=None, hop=0, pool="ball"):
         if mode not in _lib.SEG_MODES:
             raise NotImplementedError(f"GsDataset mode {mode!r}: gcn or gin")
+        if pool not in ("ball", "centre"):
+            raise ValueError(f"GsDataset pool {pool!r}: \"ball\" or \"centre\"")
         if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or hop < 0:
             raise ValueError(f"GsDataset hop {hop!r}: a non-negative integer")
         if hop >= 2**31:
@@ -161,9 +190,22 @@ class GsDataset:
         self.sub_ptr = _scan(sizes)
         self.n_member = int(self.sub_nodes.shape[0])
         self.hop = int(hop)
+        self.pool = pool
         dev = pos.device
+        self.centre_ptr, self.centre_nodes, self.n_centre = self.sub_ptr, self.sub_nodes, self.n_member
+        self.centre_sizes_h = self.centre_local = None
+        cl_min = None
         if self.hop > 0:
+            self.centre_sizes_h = sizes.cpu().numpy().astype(np.int64)  # (_balls' own read would wait for the same work)
             sizes = self._balls(n)
+            if pool == "centre":
+                self.centre_local = torch.empty(self.n_centre, dtype=torch.int32, device=dev)
+                rc = _lib.load().glass_seg_centre_index(self.centre_ptr.data_ptr(), _ptr(self.centre_nodes), self.n_sub,
+                                                        self.n_centre, self.sub_ptr.data_ptr(), _ptr(self.sub_nodes),
+                                                        self.n_member, _ptr(self.centre_local), _stream())
+                _lib.check(rc, "glass_seg_centre_index")
+                if self.n_centre:
+                    cl_min = self.centre_local.min().reshape(1)
         cnt_in = torch.empty(self.n_member, dtype=torch.int32, device=dev)
         cnt_out = torch.empty(self.n_member, dtype=torch.int32, device=dev)
         self.deg = torch.empty(self.n_member, dtype=torch.float32, device=dev) if mode == "gcn" else None
@@ -176,7 +218,16 @@ class GsDataset:
         self.rowptr_in, self.rowptr_out = _scan(cnt_in), _scan(cnt_out)
         # the split's one host sync: the row lengths every batch's row pointer and plan are built from
         self.sizes_h = sizes.cpu().numpy().astype(np.int64)
-        self.sub_ptr_h = self.sub_ptr.cpu().numpy().astype(np.int64)
+        if cl_min is None:
+            self.sub_ptr_h = self.sub_ptr.cpu().numpy().astype(np.int64)
+        else:  # the smallest centre_local rides in the same read-back
+            self.sub_ptr_h = torch.cat((self.sub_ptr, cl_min)).cpu().numpy().astype(np.int64)
+            lowest, self.sub_ptr_h = int(self.sub_ptr_h[-1]), self.sub_ptr_h[:-1]
+            if lowest < 0:
+                raise _lib.GlassHipError("glass_seg_centre_index: a centre is missing from its own ball (centre_local "
+                                         f"min {lowest})")
+        if self.centre_sizes_h is None:
+            self.centre_sizes_h = self.sizes_h
         self.cnt_in_h = cnt_in.cpu().numpy().astype(np.int64)
         self.cnt_out_h = cnt_out.cpu().numpy().astype(np.int64)
         nnz_in, nnz_out = int(self.cnt_in_h.sum()), int(self.cnt_out_h.sum())
@@ -194,8 +245,9 @@ class GsDataset:
         _lib.check(rc, "glass_seg_extract_fill")
 
     def _balls(self, n):
-        """Replaces sub_nodes / sub_ptr (the centres) by the sorted unique in-balls of radius self.hop; returns the ball
-        sizes.  One host read of the sizes, whose int64 sum is checked before anything is allocated for the fill."""
+        """Replaces sub_nodes / sub_ptr (the centres, kept as centre_nodes / centre_ptr) by the sorted unique in-balls of
+        radius self.hop; returns the ball sizes.  One host read of the sizes, whose int64 sum is checked before anything
+        is allocated for the fill."""
         b, lib, dev = self.base, _lib.load(), self.pos.device
         ws_bytes = lib.glass_seg_khop_ws_bytes(n, self.n_sub)
         if ws_bytes < 0:

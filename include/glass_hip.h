@@ -812,6 +812,37 @@ int glass_seg_khop_fill(const int32_t* in_rowptr, const int32_t* in_col, int64_t
                         const int32_t* sub_nodes, int64_t n_sub, int64_t n_member, int hops, void* ws, int64_t ws_bytes,
                         const int32_t* ball_ptr, int32_t* ball_nodes, void* stream);
 
+/*   glass_seg_centre_index / glass_seg_collate_centre: the centre marks of the hop > 0 balls and the batch that pools
+ *     over them.  GNNSeg.py:214-225 takes `inv` from k_hop_subgraph (the positions of the subgraph's own nodes in the
+ *     ball's sorted list), sets npos = zeros_like(node); npos[inv] = 1 and stores it as Data.pos: a 0/1 mark on every
+ *     ball node, 1 on a node of the subgraph itself (duplicates of a row merge into one mark).
+ *     glass_seg_centre_index, once per split: centre_ptr int32[n_sub+1] / centre_nodes int32[n_centre] are the sorted
+ *     unique centre lists (the sub_ptr / sub_nodes glass_seg_khop_* took), ball_ptr int32[n_sub+1] / ball_nodes
+ *     int32[n_ball] the balls glass_seg_khop_fill wrote.  Output centre_local int32[n_centre]: each centre's position
+ *     in its own ball's list (`inv`, ascending within a subgraph); -1 for a centre its ball does not hold (cannot
+ *     happen for the balls of glass_seg_khop_fill: a ball contains its seeds).  One workgroup per subgraph, the ball
+ *     staged in LDS when it holds <= GLASS_SEG_LDS_NODES ids and read from global memory otherwise, one centre per
+ *     lane, binary search.  Integer work, one writer per word: bitwise repeatable.
+ *     glass_seg_collate_centre, one launch per batch (GNNSeg.py:41-62): arguments and outputs of glass_seg_collate (the
+ *     block-diagonal CSR pair and node_map are bitwise the same) with sub_* the BALLS' lists and blocks, plus
+ *     centre_ptr and centre_local as above.  pos int64[n_batch, pos_width] lists, per block, only the batch rows of its
+ *     centres: node_off[b] + centre_local[centre_ptr[ids[b]] + j], ascending, -1 padding (pos_width >= the largest
+ *     centre count of the batch).  mark uint8[n_nodes]: 1 on the batch rows that are centres, 0 elsewhere — Data.pos as
+ *     PyG's collate concatenates it over the batch.  Every word of pos and every byte of mark is written.
+ *     Refused before any launch: null pointers, sizes outside [0, 2^31 - 1) (GLASS_E_ARG).  An empty split (n_sub == 0)
+ *     or batch (n_batch == 0) returns 0 without a launch. */
+int glass_seg_centre_index(const int32_t* centre_ptr, const int32_t* centre_nodes, int64_t n_sub, int64_t n_centre,
+                           const int32_t* ball_ptr, const int32_t* ball_nodes, int64_t n_ball, int32_t* centre_local,
+                           void* stream);
+int glass_seg_collate_centre(const int32_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sub,
+                             const int32_t* rowptr_in, const int32_t* col_in, const float* val_in,
+                             const int32_t* rowptr_out, const int32_t* col_out, const float* val_out,
+                             const int32_t* centre_ptr, const int32_t* centre_local, int64_t n_centre,
+                             const int32_t* ids, int64_t n_batch, const int32_t* node_off, int64_t n_nodes,
+                             const int32_t* brow_in, const int32_t* brow_out,
+                             int32_t* bcol_in, float* bval_in, int32_t* bcol_out, float* bval_out,
+                             int32_t* node_map, int64_t* pos, int64_t pos_width, uint8_t* mark, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
