@@ -15,6 +15,9 @@
 //   R4  sparse part: d jk[n] += A * g[n] on the pooled rows: an ordered, atomic-free scatter (bitwise repeatable) while
 //       pos fits LDS (B*Smax <= 16 384); beyond that float atomics (order-dependent in the last bits when subgraphs
 //       share nodes, because the row already holds the dense part).
+#include <cfloat>
+#include <climits>
+
 #include "bucket.h"
 #include "common.h"
 #include "gn_math.h"
@@ -32,6 +35,7 @@ struct ReadoutWs {
     float* dys;        // [B][C]  gradient of every pooled row of subgraph b (already scaled by the pool scale)
     float* dlogits;    // [B][K]
     float* loss_rows;  // [B]
+    int32_t* arg;      // [B][C]  max pooling only: position s within row b of pos whose node holds column c's max (-1: empty row)
 };
 
 static ReadoutWs carve_ws(void* ws, int64_t B, int64_t C, int64_t K) {
@@ -46,7 +50,14 @@ static ReadoutWs carve_ws(void* ws, int64_t B, int64_t C, int64_t K) {
     w.dlogits = (float*)p;
     p += sizeof(float) * B * K;
     w.loss_rows = (float*)p;
+    w.arg = nullptr;
     return w;
+}
+
+// max pooling: the same layout, then the [B][C] argmax block (16-B aligned: the vector consumers compare four columns per lane)
+static int64_t max_arg_offset(int64_t B, int64_t C, int64_t K) {
+    const int64_t end = (int64_t)sizeof(double) * 2 * B * C + (int64_t)sizeof(float) * (4 * C + B * C + B * K + B);
+    return (end + 15) & ~(int64_t)15;
 }
 
 __device__ __forceinline__ int valid_count(const int64_t* __restrict__ prow, int Smax, int64_t n_nodes) {
@@ -80,20 +91,30 @@ struct R1Args {
     int bwd_rep;         // (the backfill launch folds them: no reduce launch in between)
 };
 
-// dynamic LDS (floats): sums[2C doubles] | coef_s[2C] | mu_rstd_s[2C] | pooled_s[C] | xh_s[C] | red[kBlock*8] |
-// zs[kReadoutMaxK] | dl[kReadoutMaxK]
+// dynamic LDS (floats): sums[2C doubles] | coef_s[2C] | mu_rstd_s[2C] | pooled_s[C] | xh_s[C] | (MAX: arg_s[C]) |
+// red[kBlock*8, MAX: kBlock*12] | zs[kReadoutMaxK] | dl[kReadoutMaxK]
 // VW = floats per lane and access: 4 (C % 4 == 0, 16-B aligned rows) or 1 (any C: the 17-wide layers of config/component.yml)
-template <int VW>
+// MAX: max pooling over the GraphNorm OUTPUT y = scale*x + shift (gamma may be negative) with the semantics of pool.hip's
+// pool_fwd_kernel: strict compare, on a tie the lowest position s of the row wins (so a node listed twice counts at its first
+// position), padding / out-of-range ids skipped, an empty row pools to 0 with no gradient.  A slot keeps a running
+// (max, s, xhat at the max); only the winner's row carries the column's gradient, so the subgraph's share of the backward
+// column sums is S1 += dy, S2 += dy * xhat[argmax].
+constexpr int readout_lds_head(bool mx) { return mx ? 11 : 10; }  // C-sized float arrays in front of red
+constexpr int readout_red_stride(bool mx) { return mx ? 12 : 8; }  // floats per thread in red (MAX: + 4 argmax lanes)
+
+template <int VW, bool MAX>
 __global__ __launch_bounds__(kBlock) void readout_subgraph_kernel(R1Args a) {
     extern __shared__ float sm[];
     const int C = a.C, K = a.K;
+    constexpr int RS = readout_red_stride(MAX);
     double* sums = reinterpret_cast<double*>(sm);
     float* coef_s = sm + 4 * C;
     float* mu_rstd_s = sm + 6 * C;
     float* pooled_s = sm + 8 * C;
     float* xh_s = sm + 9 * C;
-    float* red = sm + 10 * C;
-    float* zs = red + kBlock * 8;
+    [[maybe_unused]] int* arg_s = reinterpret_cast<int*>(sm + 10 * C);  // (MAX)
+    float* red = sm + readout_lds_head(MAX) * C;
+    float* zs = red + kBlock * RS;
     float* dl = zs + kReadoutMaxK;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int64_t* prow = a.pos + (int64_t)b * a.Smax;
@@ -141,6 +162,10 @@ __global__ __launch_bounds__(kBlock) void readout_subgraph_kernel(R1Args a) {
     const int c0 = tc * VW;
     const bool ok = c0 < C;
     float accy[4] = {0.f, 0.f, 0.f, 0.f}, acch[4] = {0.f, 0.f, 0.f, 0.f};
+    [[maybe_unused]] int best[4] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX};  // (MAX) position of accy; acch = xhat there
+    if constexpr (MAX)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) accy[k] = -FLT_MAX;
     if (ok) {
         float mu[VW], rstd[VW], scale[VW], shift[VW], al[VW];
 #pragma unroll
@@ -165,8 +190,17 @@ __global__ __launch_bounds__(kBlock) void readout_subgraph_kernel(R1Args a) {
                 }
 #pragma unroll
                 for (int k = 0; k < VW; ++k) {
-                    accy[k] += fmaf(x[k], scale[k], shift[k]);
-                    acch[k] += (x[k] - al[k] * mu[k]) * rstd[k];
+                    if constexpr (MAX) {
+                        const float y = fmaf(x[k], scale[k], shift[k]);
+                        if (y > accy[k]) {  // strict, j ascending within the slot: the first occurrence wins a tie
+                            accy[k] = y;
+                            acch[k] = (x[k] - al[k] * mu[k]) * rstd[k];
+                            best[k] = j;
+                        }
+                    } else {
+                        accy[k] += fmaf(x[k], scale[k], shift[k]);
+                        acch[k] += (x[k] - al[k] * mu[k]) * rstd[k];
+                    }
                 }
             }
         } else {
@@ -199,8 +233,17 @@ __global__ __launch_bounds__(kBlock) void readout_subgraph_kernel(R1Args a) {
                     if (!live[u]) continue;
 #pragma unroll
                     for (int k = 0; k < VW; ++k) {
-                        accy[k] += fmaf(x[u][k], scale[k], shift[k]);
-                        acch[k] += (x[u][k] - al[k] * mu[k]) * rstd[k];
+                        if constexpr (MAX) {
+                            const float y = fmaf(x[u][k], scale[k], shift[k]);
+                            if (y > accy[k]) {
+                                accy[k] = y;
+                                acch[k] = (x[u][k] - al[k] * mu[k]) * rstd[k];
+                                best[k] = j0 + u * rpb;
+                            }
+                        } else {
+                            accy[k] += fmaf(x[u][k], scale[k], shift[k]);
+                            acch[k] += (x[u][k] - al[k] * mu[k]) * rstd[k];
+                        }
                     }
                 }
             }
@@ -208,22 +251,43 @@ __global__ __launch_bounds__(kBlock) void readout_subgraph_kernel(R1Args a) {
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        red[tid * 8 + k] = accy[k];
-        red[tid * 8 + 4 + k] = acch[k];
+        red[tid * RS + k] = accy[k];
+        red[tid * RS + 4 + k] = acch[k];
+        if constexpr (MAX) reinterpret_cast<int*>(red)[tid * RS + 8 + k] = best[k];
     }
     __syncthreads();
     if (tr == 0 && ok) {
         for (int r = 1; r < rpb; ++r)
 #pragma unroll
             for (int k = 0; k < VW; ++k) {
-                accy[k] += red[(r * TC + tc) * 8 + k];
-                acch[k] += red[(r * TC + tc) * 8 + 4 + k];
+                if constexpr (MAX) {
+                    const float ov = red[(r * TC + tc) * RS + k];
+                    const int oj = reinterpret_cast<const int*>(red)[(r * TC + tc) * RS + 8 + k];
+                    if (ov > accy[k] || (ov == accy[k] && oj < best[k])) {  // (value, then lower s): pool.hip's rule
+                        accy[k] = ov;
+                        acch[k] = red[(r * TC + tc) * RS + 4 + k];
+                        best[k] = oj;
+                    }
+                } else {
+                    accy[k] += red[(r * TC + tc) * RS + k];
+                    acch[k] += red[(r * TC + tc) * RS + 4 + k];
+                }
             }
 #pragma unroll
         for (int k = 0; k < VW; ++k) {
-            pooled_s[c0 + k] = accy[k] * sc;
-            xh_s[c0 + k] = acch[k];
-            a.pooled[(int64_t)b * C + c0 + k] = accy[k] * sc;
+            if constexpr (MAX) {
+                const bool any = best[k] != INT32_MAX;  // empty row (or no finite entry): pooled 0, no gradient
+                const float pv = any ? accy[k] : 0.f;
+                pooled_s[c0 + k] = pv;
+                xh_s[c0 + k] = any ? acch[k] : 0.f;
+                arg_s[c0 + k] = any ? best[k] : -1;
+                a.pooled[(int64_t)b * C + c0 + k] = pv;
+                a.ws.arg[(int64_t)b * C + c0 + k] = any ? best[k] : -1;
+            } else {
+                pooled_s[c0 + k] = accy[k] * sc;
+                xh_s[c0 + k] = acch[k];
+                a.pooled[(int64_t)b * C + c0 + k] = accy[k] * sc;
+            }
         }
     }
     __syncthreads();
@@ -282,11 +346,14 @@ __global__ __launch_bounds__(kBlock) void readout_subgraph_kernel(R1Args a) {
         for (int k = 0; k < K; ++k) s = fmaf(dl[k], a.Wh[(int64_t)k * C + c], s);
         const float dy = sc * s;
         a.ws.dys[(int64_t)b * C + c] = dy;
+        // rows of the subgraph that carry dy: all cnt of them — or (MAX) the one at the column's argmax (xh_s = its xhat)
+        double rows;
+        if constexpr (MAX) rows = arg_s[c] >= 0 ? 1.0 : 0.0; else rows = (double)cnt;
         if (a.bwd_acc) {
-            gn_acc_add(a.bwd_acc, b % a.bwd_rep, 0, c, C, (double)cnt * (double)dy, kAccScaleBwd);
+            gn_acc_add(a.bwd_acc, b % a.bwd_rep, 0, c, C, rows * (double)dy, kAccScaleBwd);
             gn_acc_add(a.bwd_acc, b % a.bwd_rep, 1, c, C, (double)dy * (double)xh_s[c], kAccScaleBwd);
         } else {
-            part[c] = (double)cnt * (double)dy;
+            part[c] = rows * (double)dy;
             part[C + c] = (double)dy * (double)xh_s[c];
         }
     }
@@ -380,11 +447,22 @@ __global__ __launch_bounds__(kBlock) void readout_dense_kernel(const float* __re
 // read-modify-write of that row.  Bitwise repeatable however many subgraphs share a node; B*Smax <= 16 384.
 constexpr int kOrdBlock = 1024;  // 16 waves: one entry per wave for Smax <= 16, so the per-entry latency chains overlap
 
+// MAX (every consumer of dys below): entry (b, s) carries column c of dys[b] only where arg[b][c] == s — the subgraph
+// kernel's argmax position; the vector forms compare four columns per lane.  The order of the sum stays (b, s) ascending.
+__device__ __forceinline__ void fma4_where(const float4& A, const float4& g, const int4& ar, int s, float4& acc) {
+    if (ar.x == s) acc.x = fmaf(A.x, g.x, acc.x);
+    if (ar.y == s) acc.y = fmaf(A.y, g.y, acc.y);
+    if (ar.z == s) acc.z = fmaf(A.z, g.z, acc.z);
+    if (ar.w == s) acc.w = fmaf(A.w, g.w, acc.w);
+}
+
+template <bool MAX>
 __global__ __launch_bounds__(kOrdBlock) void readout_scatter_ordered_kernel(const int64_t* __restrict__ pos, int Smax,
                                                                          int n_pos, const float* __restrict__ dys,
                                                                          const float* __restrict__ coef,
                                                                          float* __restrict__ dx, int64_t lddx,
-                                                                         int64_t n_nodes, int C) {
+                                                                         int64_t n_nodes, int C,
+                                                                         const int32_t* __restrict__ arg) {
     extern __shared__ int32_t nodes[];
     for (int j = threadIdx.x; j < n_pos; j += kOrdBlock) {
         const int64_t p = pos[j];
@@ -418,16 +496,22 @@ __global__ __launch_bounds__(kOrdBlock) void readout_scatter_ordered_kernel(cons
                 const int bit = __ffsll((long long)hits) - 1;
                 hits &= hits - 1;
                 const float* grow = dys + (int64_t)((j0 + bit) / Smax) * C;
+                [[maybe_unused]] const int32_t* arow = arg + (int64_t)((j0 + bit) / Smax) * C;  // (MAX)
+                [[maybe_unused]] const int spos = (j0 + bit) % Smax;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const int c = lane * 4 + kWave * 4 * t;
                     if (c < C) {
                         const float4 A = *reinterpret_cast<const float4*>(coef + c);
                         const float4 g = *reinterpret_cast<const float4*>(grow + c);
-                        acc[t].x = fmaf(A.x, g.x, acc[t].x);
-                        acc[t].y = fmaf(A.y, g.y, acc[t].y);
-                        acc[t].z = fmaf(A.z, g.z, acc[t].z);
-                        acc[t].w = fmaf(A.w, g.w, acc[t].w);
+                        if constexpr (MAX) {
+                            fma4_where(A, g, *reinterpret_cast<const int4*>(arow + c), spos, acc[t]);
+                        } else {
+                            acc[t].x = fmaf(A.x, g.x, acc[t].x);
+                            acc[t].y = fmaf(A.y, g.y, acc[t].y);
+                            acc[t].z = fmaf(A.z, g.z, acc[t].z);
+                            acc[t].w = fmaf(A.w, g.w, acc[t].w);
+                        }
                     }
                 }
             }
@@ -467,6 +551,7 @@ struct BackfillFin {
     float* loss_sum;  // nullable: += the step's loss
 };
 
+template <bool MAX>
 __global__ __launch_bounds__(kOrdBlock) void readout_backfill_kernel(const float* __restrict__ x, int64_t ldx,
                                                                     float* __restrict__ dx, int64_t lddx, int64_t N, int C,
                                                                     int tc_log2, const float* __restrict__ coef,
@@ -475,7 +560,7 @@ __global__ __launch_bounds__(kOrdBlock) void readout_backfill_kernel(const float
                                                                     const float* __restrict__ dys,
                                                                     const int32_t* __restrict__ lab_rows,
                                                                     const int32_t* __restrict__ lab_count, int n_dense, int n_sparse,
-                                                                    BackfillFin fin) {
+                                                                    BackfillFin fin, const int32_t* __restrict__ arg) {
     extern __shared__ int32_t nodes[];
     const int tid = threadIdx.x;
     if ((int)blockIdx.x >= n_dense + n_sparse) {  // head gradient row k, or the mean loss (two-launch form)
@@ -578,16 +663,22 @@ __global__ __launch_bounds__(kOrdBlock) void readout_backfill_kernel(const float
             const int bit = __ffsll((long long)hits) - 1;
             hits &= hits - 1;
             const float* grow = dys + (int64_t)((j0 + bit) / Smax) * C;
+            [[maybe_unused]] const int32_t* arow = arg + (int64_t)((j0 + bit) / Smax) * C;  // (MAX)
+            [[maybe_unused]] const int spos = (j0 + bit) % Smax;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int c = lane * 4 + kWave * 4 * t;
                 if (c < C) {
                     const float4 A = *reinterpret_cast<const float4*>(cf + c);
                     const float4 g = *reinterpret_cast<const float4*>(grow + c);
-                    acc[t].x = fmaf(A.x, g.x, acc[t].x);
-                    acc[t].y = fmaf(A.y, g.y, acc[t].y);
-                    acc[t].z = fmaf(A.z, g.z, acc[t].z);
-                    acc[t].w = fmaf(A.w, g.w, acc[t].w);
+                    if constexpr (MAX) {
+                        fma4_where(A, g, *reinterpret_cast<const int4*>(arow + c), spos, acc[t]);
+                    } else {
+                        acc[t].x = fmaf(A.x, g.x, acc[t].x);
+                        acc[t].y = fmaf(A.y, g.y, acc[t].y);
+                        acc[t].z = fmaf(A.z, g.z, acc[t].z);
+                        acc[t].w = fmaf(A.w, g.w, acc[t].w);
+                    }
                 }
             }
         }
@@ -609,12 +700,14 @@ __global__ __launch_bounds__(kOrdBlock) void readout_backfill_kernel(const float
 // R3 + R4 for ANY C (scalar accesses; the 17-wide layers of config/component.yml): one wave per node, lanes over the
 // columns; a labeled (= pooled) node walks the padded pos matrix in (b, s) order and adds A * g of every subgraph that holds
 // it — atomic-free, bitwise repeatable, no size limit on pos.
+template <bool MAX>
 __global__ __launch_bounds__(kBlock) void readout_backfill_scalar_kernel(const float* __restrict__ x, int64_t ldx,
                                                                         float* __restrict__ dx, int64_t lddx, int64_t N, int C,
                                                                         const float* __restrict__ coef,
                                                                         const uint8_t* __restrict__ mask,
                                                                         const int64_t* __restrict__ pos, int Smax, int n_pos,
-                                                                        const float* __restrict__ dys) {
+                                                                        const float* __restrict__ dys,
+                                                                        const int32_t* __restrict__ arg) {
     const int lane = threadIdx.x & 63;
     const int64_t node = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
     if (node >= N) return;
@@ -622,8 +715,14 @@ __global__ __launch_bounds__(kBlock) void readout_backfill_scalar_kernel(const f
     for (int c = lane; c < C; c += kWave) {
         float acc = 0.f;
         if (lab)
-            for (int j = 0; j < n_pos; ++j)
-                if (pos[j] == node) acc = fmaf(coef[c], dys[(int64_t)(j / Smax) * C + c], acc);
+            for (int j = 0; j < n_pos; ++j) {
+                if constexpr (MAX) {
+                    if (pos[j] == node && arg[(int64_t)(j / Smax) * C + c] == j % Smax)
+                        acc = fmaf(coef[c], dys[(int64_t)(j / Smax) * C + c], acc);
+                } else {
+                    if (pos[j] == node) acc = fmaf(coef[c], dys[(int64_t)(j / Smax) * C + c], acc);
+                }
+            }
         dx[node * lddx + c] = fmaf(coef[C + c], x[node * ldx + c], coef[2 * C + c]) + acc;
     }
 }
@@ -632,10 +731,22 @@ __global__ __launch_bounds__(kBlock) void readout_backfill_scalar_kernel(const f
 // pooled node's row gets  d jk[n] += sum over its entries of A * g[subgraph]  with the sum taken in exact fixed point — the
 // lists' arbitrary order does not reach the result.  One lane group (16 B per lane) per node; long lists by the whole
 // workgroup.  The dense part (readout_dense_kernel) wrote every row before.
+// MAX: the lists are deduplicated per row (a node is listed once for a subgraph that names it twice) and an entry adds
+// column c only where the subgraph's argmax position for c names this node.
+__device__ __forceinline__ void exact_add4_where(ExactSum* s, const float4& A, const float4& g, const int4& ar,
+                                                 const int64_t* __restrict__ prow, int64_t node) {
+    if (ar.x >= 0 && prow[ar.x] == node) s[0].add(A.x * g.x);
+    if (ar.y >= 0 && prow[ar.y] == node) s[1].add(A.y * g.y);
+    if (ar.z >= 0 && prow[ar.z] == node) s[2].add(A.z * g.z);
+    if (ar.w >= 0 && prow[ar.w] == node) s[3].add(A.w * g.w);
+}
+
+template <bool MAX>
 __global__ __launch_bounds__(kBlock) void readout_gather_add_kernel(const int32_t* __restrict__ off, const int32_t* __restrict__ list,
                                                                     const float* __restrict__ dys, const float* __restrict__ coef,
                                                                     float* __restrict__ dx, int64_t lddx, int64_t n_nodes, int C,
-                                                                    int tc_log2) {
+                                                                    int tc_log2, const int32_t* __restrict__ arg,
+                                                                    const int64_t* __restrict__ pos, int Smax) {
     __shared__ long long red[kBlock * 4 * 2];
     const int G = 1 << tc_log2, li = threadIdx.x & (G - 1), slot = threadIdx.x >> tc_log2, n_slot = kBlock >> tc_log2;
     const int64_t node0 = (int64_t)blockIdx.x * n_slot;
@@ -652,7 +763,12 @@ __global__ __launch_bounds__(kBlock) void readout_gather_add_kernel(const int32_
             for (int k = 0; k < 4; ++k) s[k].hi = s[k].lo = 0;
             for (int i = beg; i < end; ++i) {
                 const float4 g = *reinterpret_cast<const float4*>(dys + (int64_t)list[i] * C + c0);
-                s[0].add(A.x * g.x); s[1].add(A.y * g.y); s[2].add(A.z * g.z); s[3].add(A.w * g.w);
+                if constexpr (MAX)
+                    exact_add4_where(s, A, g, *reinterpret_cast<const int4*>(arg + (int64_t)list[i] * C + c0),
+                                     pos + (int64_t)list[i] * Smax, node);
+                else {
+                    s[0].add(A.x * g.x); s[1].add(A.y * g.y); s[2].add(A.z * g.z); s[3].add(A.w * g.w);
+                }
             }
             float4* d = reinterpret_cast<float4*>(dx + node * lddx + c0);
             float4 o = *d;
@@ -671,7 +787,12 @@ __global__ __launch_bounds__(kBlock) void readout_gather_add_kernel(const int32_
         if (ok)
             for (int i = beg + slot; i < end; i += n_slot) {
                 const float4 g = *reinterpret_cast<const float4*>(dys + (int64_t)list[i] * C + c0);
-                s[0].add(A.x * g.x); s[1].add(A.y * g.y); s[2].add(A.z * g.z); s[3].add(A.w * g.w);
+                if constexpr (MAX)
+                    exact_add4_where(s, A, g, *reinterpret_cast<const int4*>(arg + (int64_t)list[i] * C + c0),
+                                     pos + (int64_t)list[i] * Smax, node);
+                else {
+                    s[0].add(A.x * g.x); s[1].add(A.y * g.y); s[2].add(A.z * g.z); s[3].add(A.w * g.w);
+                }
             }
         __syncthreads();
 #pragma unroll
@@ -720,23 +841,35 @@ extern "C" int64_t glass_readout_scatter_ws_bytes(int64_t n_nodes, int64_t B, in
     return (int64_t)sizeof(int32_t) * bucket_ws_words(n_nodes, B, Smax, false);
 }
 
-extern "C" int glass_readout_train_f32(const float* jk, int64_t ldj, const float* gn_saved, const float* gamma,
-                                       const float* alpha, const int64_t* pos, int64_t B, int64_t Smax, int pool_mode,
-                                       const float* Wh, const float* bh, const void* target, int loss_mode, int64_t K,
-                                       const float* grad_loss, float* pooled, float* logits, float* loss, float* djk,
-                                       int64_t lddj, float* dWh, float* dbh, int acc_head, float* dgamma, float* dbeta,
-                                       float* dalpha, int acc_gn, void* ws, int64_t n_nodes, int64_t C,
-                                       const uint8_t* mask, const int32_t* lab_rows, const int32_t* lab_count,
-                                       const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
-                                       float* loss_sum, void* stream) {
+extern "C" int glass_readout_max_supported(int64_t C, int64_t K) {
+    return (C > 0 && C <= 4 * kBlock && K > 0 && K <= kReadoutMaxK) ? 1 : 0;
+}
+
+extern "C" int64_t glass_readout_max_ws_bytes(int64_t B, int64_t C, int64_t K) {
+    if (B <= 0 || C <= 0 || K <= 0) return GLASS_E_ARG;
+    return max_arg_offset(B, C, K) + (int64_t)sizeof(int32_t) * B * C + 64;
+}
+
+// both entries: MAX selects the max instantiations and the workspace with the argmax block (pool_mode is then GLASS_POOL_MAX)
+template <bool MAX>
+static int readout_train(const char* what, const float* jk, int64_t ldj, const float* gn_saved, const float* gamma,
+                         const float* alpha, const int64_t* pos, int64_t B, int64_t Smax, int pool_mode,
+                         const float* Wh, const float* bh, const void* target, int loss_mode, int64_t K,
+                         const float* grad_loss, float* pooled, float* logits, float* loss, float* djk,
+                         int64_t lddj, float* dWh, float* dbh, int acc_head, float* dgamma, float* dbeta,
+                         float* dalpha, int acc_gn, void* ws, int64_t n_nodes, int64_t C,
+                         const uint8_t* mask, const int32_t* lab_rows, const int32_t* lab_count,
+                         const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
+                         float* loss_sum, void* stream) {
     GLASS_REQUIRE(jk && gn_saved && gamma && alpha && pos && Wh && bh && target && grad_loss && pooled && logits && loss &&
                       djk && dWh && dbh && ws,
                   "readout_train: null pointer");
     GLASS_REQUIRE(B > 0 && Smax > 0 && Smax < (1ll << 31) && n_nodes > 0 && ldj >= C && lddj >= C && B * K < (1ll << 30),
                   "readout_train: bad sizes");
-    if (!glass_readout_supported(C, K, pool_mode) || (loss_mode != kLossCE && loss_mode != kLossBCE)) {
+    if (!(MAX ? glass_readout_max_supported(C, K) : glass_readout_supported(C, K, pool_mode)) ||
+        (loss_mode != kLossCE && loss_mode != kLossBCE)) {
         set_error("readout_train: unsupported shape/mode (C=%lld K=%lld pool=%d loss=%d): C %% 4 == 0, C <= 1024, "
-                  "K <= 256, pool sum|mean|size", (long long)C, (long long)K, pool_mode, loss_mode);
+                  "K <= 256, pool sum|mean|size (max: glass_readout_max_train_f32)", (long long)C, (long long)K, pool_mode, loss_mode);
         return GLASS_E_UNSUPPORTED;
     }
     const bool vec = C % 4 == 0 && ldj % 4 == 0 && lddj % 4 == 0 && aligned16(jk) && aligned16(djk) && aligned16(pooled);
@@ -750,7 +883,8 @@ extern "C" int glass_readout_train_f32(const float* jk, int64_t ldj, const float
         return GLASS_E_WS;
     }
     hipStream_t st = (hipStream_t)stream;
-    const ReadoutWs w = carve_ws(ws, B, C, K);
+    ReadoutWs w = carve_ws(ws, B, C, K);
+    if (MAX) w.arg = reinterpret_cast<int32_t*>((char*)ws + max_arg_offset(B, C, K));
     const int tc = pow2_ceil_cap(vec ? C / 4 : C, kBlock);
     int tc_log2 = 0;
     while ((1 << tc_log2) < tc) ++tc_log2;
@@ -767,15 +901,16 @@ extern "C" int glass_readout_train_f32(const float* jk, int64_t ldj, const float
     const bool two = gn_bwd_acc != nullptr && vec && mask && lab_rows && lab_count && B * Smax <= kReadoutOrderedMax;
     GLASS_REQUIRE(!gn_bwd_acc || (gn_bwd_rep >= 1 && gn_bwd_rep <= kAccRep), "readout_train: gn_bwd_rep = replicas of gn_bwd_acc (1 .. 16)");
     // long subgraphs: the row's node ids staged in LDS by the counting pass (while everything stays within 64 KB)
-    const int stash = Smax > 2 * (kBlock >> tc_log2) && n_nodes < (1ll << 31) && sizeof(float) * (size_t)(10 * C + kBlock * 8 + 2 * kReadoutMaxK + Smax) <= 64 * 1024;
+    const size_t lds1_base = sizeof(float) * (size_t)(readout_lds_head(MAX) * C + kBlock * readout_red_stride(MAX) + 2 * kReadoutMaxK);
+    const int stash = Smax > 2 * (kBlock >> tc_log2) && n_nodes < (1ll << 31) && lds1_base + sizeof(float) * (size_t)Smax <= 64 * 1024;
     R1Args a1{jk, ldj, gn_saved, alpha, pos, (int)Smax, pool_mode, Wh, bh, target, loss_mode, (int)B, (int)C, (int)K,
               grad_loss, pooled, logits, w, n_nodes, tc_log2, esrc, stash, two ? reinterpret_cast<long long*>(gn_bwd_acc) : nullptr,
               gn_bwd_rep};
-    const size_t lds1 = sizeof(float) * (size_t)(10 * C + kBlock * 8 + 2 * kReadoutMaxK + (stash ? Smax : 0));
+    const size_t lds1 = lds1_base + sizeof(float) * (size_t)(stash ? Smax : 0);
     if (vec)
-        hipLaunchKernelGGL(readout_subgraph_kernel<4>, dim3((unsigned)B), dim3(kBlock), lds1, st, a1);
+        hipLaunchKernelGGL((readout_subgraph_kernel<4, MAX>), dim3((unsigned)B), dim3(kBlock), lds1, st, a1);
     else
-        hipLaunchKernelGGL(readout_subgraph_kernel<1>, dim3((unsigned)B), dim3(kBlock), lds1, st, a1);
+        hipLaunchKernelGGL((readout_subgraph_kernel<1, MAX>), dim3((unsigned)B), dim3(kBlock), lds1, st, a1);
     R2Args a2{pooled, w, (int)B, (int)C, (int)K, loss_mode, dWh, dbh, acc_head, loss, loss_sum, n_nodes, gamma, alpha, gn_saved,
               dgamma, dbeta, dalpha, acc_gn};
     size_t lds2 = sizeof(double) * kBlock * 2;
@@ -783,9 +918,9 @@ extern "C" int glass_readout_train_f32(const float* jk, int64_t ldj, const float
     GLASS_REQUIRE(lds2 <= 64 * 1024, "readout_train: batch too large for the LDS staging");
     if (!two) hipLaunchKernelGGL(readout_reduce_kernel, dim3((unsigned)(K + 1 + ceil_div(C, kFinCols))), dim3(kBlock), lds2, st, a2);
     if (!vec) {  // any C: scalar dense + sparse part as one launch (needs the label bytes = the pooled rows of this pos)
-        hipLaunchKernelGGL(readout_backfill_scalar_kernel, dim3((unsigned)ceil_div(n_nodes, kBlock / kWave)), dim3(kBlock), 0, st,
-                           jk, ldj, djk, lddj, n_nodes, (int)C, w.coef, mask, pos, (int)Smax, (int)(B * Smax), w.dys);
-        return launch_status("glass_readout_train_f32");
+        hipLaunchKernelGGL(readout_backfill_scalar_kernel<MAX>, dim3((unsigned)ceil_div(n_nodes, kBlock / kWave)), dim3(kBlock), 0, st,
+                           jk, ldj, djk, lddj, n_nodes, (int)C, w.coef, mask, pos, (int)Smax, (int)(B * Smax), w.dys, w.arg);
+        return launch_status(what);
     }
     if (mask && lab_rows && lab_count && B * Smax <= kReadoutOrderedMax) {
         // the pooled rows are listed (glass_batch_labels on this pos): dense and sparse part as ONE launch
@@ -803,12 +938,12 @@ extern "C" int glass_readout_train_f32(const float* jk, int64_t ldj, const float
             if (lds3 < sizeof(float) * (size_t)B) lds3 = sizeof(float) * (size_t)B;
             extra = (unsigned)K + 1;
             if (lds3 > 64 * 1024)
-                (void)hipFuncSetAttribute((const void*)readout_backfill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
+                (void)hipFuncSetAttribute((const void*)readout_backfill_kernel<MAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
         }
-        hipLaunchKernelGGL(readout_backfill_kernel, dim3((unsigned)(n_dense + n_sparse) + extra), dim3(kOrdBlock), lds3, st, jk, ldj, djk,
+        hipLaunchKernelGGL(readout_backfill_kernel<MAX>, dim3((unsigned)(n_dense + n_sparse) + extra), dim3(kOrdBlock), lds3, st, jk, ldj, djk,
                            lddj, n_nodes, (int)C, tc_log2, w.coef, mask, pos, (int)Smax, (int)(B * Smax), w.dys, lab_rows, lab_count,
-                           (int)n_dense, (int)n_sparse, fin);
-        return launch_status("glass_readout_train_f32");
+                           (int)n_dense, (int)n_sparse, fin, w.arg);
+        return launch_status(what);
     }
     const int rpb = kBlock / tc;
     int64_t blocks = ceil_div(n_nodes, (int64_t)rpb * 4);
@@ -817,15 +952,45 @@ extern "C" int glass_readout_train_f32(const float* jk, int64_t ldj, const float
                        tc_log2, w.coef);
     if (B * Smax <= kReadoutOrderedMax) {
         const int64_t parts = ceil_div(Smax, (int64_t)(kOrdBlock / kWave));
-        hipLaunchKernelGGL(readout_scatter_ordered_kernel, dim3((unsigned)(B * parts)), dim3(kOrdBlock), sizeof(int32_t) * (size_t)(B * Smax),
-                           st, pos, (int)Smax, (int)(B * Smax), w.dys, w.coef, djk, lddj, n_nodes, (int)C);
+        hipLaunchKernelGGL(readout_scatter_ordered_kernel<MAX>, dim3((unsigned)(B * parts)), dim3(kOrdBlock), sizeof(int32_t) * (size_t)(B * Smax),
+                           st, pos, (int)Smax, (int)(B * Smax), w.dys, w.coef, djk, lddj, n_nodes, (int)C, w.arg);
     } else if (scatter_ws) {
         // exact, atomic-free: entries bucketed by node, then one gather-add per pooled node (glass_readout_scatter_ws_bytes)
         BucketLists bl;
-        int rc = bucket_build(pos, B, Smax, -1, false, n_nodes, scatter_ws, st, &bl);
+        int rc = bucket_build(pos, B, Smax, -1, false, n_nodes, scatter_ws, st, &bl, MAX);  // (MAX: a node once per row)
         if (rc) return rc;
-        hipLaunchKernelGGL(readout_gather_add_kernel, dim3((unsigned)ceil_div(n_nodes, (int64_t)(kBlock / tc))), dim3(kBlock), 0, st,
-                           bl.off, bl.list, w.dys, w.coef, djk, lddj, n_nodes, (int)C, tc_log2);
+        hipLaunchKernelGGL(readout_gather_add_kernel<MAX>, dim3((unsigned)ceil_div(n_nodes, (int64_t)(kBlock / tc))), dim3(kBlock), 0, st,
+                           bl.off, bl.list, w.dys, w.coef, djk, lddj, n_nodes, (int)C, tc_log2, w.arg, pos, (int)Smax);
     }
-    return launch_status("glass_readout_train_f32");
+    return launch_status(what);
+}
+
+#define GLASS_READOUT_ARGS                                                                                                   \
+    jk, ldj, gn_saved, gamma, alpha, pos, B, Smax, pool_mode, Wh, bh, target, loss_mode, K, grad_loss, pooled, logits, loss, \
+        djk, lddj, dWh, dbh, acc_head, dgamma, dbeta, dalpha, acc_gn, ws, n_nodes, C, mask, lab_rows, lab_count, gn_src,     \
+        gn_bwd_acc, gn_bwd_rep, scatter_ws, loss_sum, stream
+
+extern "C" int glass_readout_train_f32(const float* jk, int64_t ldj, const float* gn_saved, const float* gamma,
+                                       const float* alpha, const int64_t* pos, int64_t B, int64_t Smax, int pool_mode,
+                                       const float* Wh, const float* bh, const void* target, int loss_mode, int64_t K,
+                                       const float* grad_loss, float* pooled, float* logits, float* loss, float* djk,
+                                       int64_t lddj, float* dWh, float* dbh, int acc_head, float* dgamma, float* dbeta,
+                                       float* dalpha, int acc_gn, void* ws, int64_t n_nodes, int64_t C,
+                                       const uint8_t* mask, const int32_t* lab_rows, const int32_t* lab_count,
+                                       const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
+                                       float* loss_sum, void* stream) {
+    return readout_train<false>("glass_readout_train_f32", GLASS_READOUT_ARGS);
+}
+
+extern "C" int glass_readout_max_train_f32(const float* jk, int64_t ldj, const float* gn_saved, const float* gamma,
+                                           const float* alpha, const int64_t* pos, int64_t B, int64_t Smax,
+                                           const float* Wh, const float* bh, const void* target, int loss_mode, int64_t K,
+                                           const float* grad_loss, float* pooled, float* logits, float* loss, float* djk,
+                                           int64_t lddj, float* dWh, float* dbh, int acc_head, float* dgamma, float* dbeta,
+                                           float* dalpha, int acc_gn, void* ws, int64_t n_nodes, int64_t C,
+                                           const uint8_t* mask, const int32_t* lab_rows, const int32_t* lab_count,
+                                           const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
+                                           float* loss_sum, void* stream) {
+    const int pool_mode = GLASS_POOL_MAX;
+    return readout_train<true>("glass_readout_max_train_f32", GLASS_READOUT_ARGS);
 }

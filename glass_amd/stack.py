@@ -732,7 +732,9 @@ class StackProgram:
         final = st["final_saved"]  # (kept alive across the call below: the glass_gn_src struct lives in it)
         saved, src = _saved_args(final)
         st["final_saved"] = getattr(final, "saved", final)
-        ws = torch.empty(lib.glass_readout_ws_bytes(B, C, K) // 8 + 1, dtype=torch.float64, device=dev)
+        mx = pool_mode == "max"  # entries of its own: the workspace ends with the [B][C] argmax block, no pool_mode argument
+        ws_bytes = lib.glass_readout_max_ws_bytes(B, C, K) if mx else lib.glass_readout_ws_bytes(B, C, K)
+        ws = torch.empty(ws_bytes // 8 + 1, dtype=torch.float64, device=dev)
         pooled, logits = torch.empty((B, C), **f32), torch.empty((B, K), **f32)
         loss, djk = torch.empty((), **f32), torch.empty((n, C), **f32)
         tgt = target.contiguous().to(torch.int64 if loss_mode == 0 else torch.float32)
@@ -742,16 +744,19 @@ class StackProgram:
             labels = BatchLabels(n, pos.numel(), dev)
             labels.load(pos)
         largs = (0, 0, 0) if labels is None else (labels.mask.data_ptr(), labels.rows.data_ptr(), labels.count.data_ptr())
-        _check(lib.glass_readout_train_f32(jk.data_ptr(), jk.stride(0), saved, gn.weight.data_ptr(),
-                                           gn.mean_scale.data_ptr(), pos.data_ptr(), B, Smax, _lib.POOL_MODES[pool_mode],
-                                           head.weight.data_ptr(), head.bias.data_ptr(), tgt.data_ptr(), loss_mode, K,
-                                           _one(dev).data_ptr(), pooled.data_ptr(), logits.data_ptr(), loss.data_ptr(),
-                                           djk.data_ptr(), djk.stride(0), head.weight.grad.data_ptr(),
-                                           head.bias.grad.data_ptr(), st["acc"], gn.weight.grad.data_ptr(),
-                                           gn.bias.grad.data_ptr(), gn.mean_scale.grad.data_ptr(), st["acc"], ws.data_ptr(),
-                                           n, C, *largs, src, 0 if acc_ro is None else acc_ro.data_ptr(), REP_DENSE, sws,
-                                           0 if self.loss_sum is None else self.loss_sum.data_ptr(), _stream()),
-               "glass_readout_train_f32")
+        entry, name = ((lib.glass_readout_max_train_f32, "glass_readout_max_train_f32") if mx else
+                       (lib.glass_readout_train_f32, "glass_readout_train_f32"))
+        mode_arg = () if mx else (_lib.POOL_MODES[pool_mode], )
+        _check(entry(jk.data_ptr(), jk.stride(0), saved, gn.weight.data_ptr(),
+                     gn.mean_scale.data_ptr(), pos.data_ptr(), B, Smax, *mode_arg,
+                     head.weight.data_ptr(), head.bias.data_ptr(), tgt.data_ptr(), loss_mode, K,
+                     _one(dev).data_ptr(), pooled.data_ptr(), logits.data_ptr(), loss.data_ptr(),
+                     djk.data_ptr(), djk.stride(0), head.weight.grad.data_ptr(),
+                     head.bias.grad.data_ptr(), st["acc"], gn.weight.grad.data_ptr(),
+                     gn.bias.grad.data_ptr(), gn.mean_scale.grad.data_ptr(), st["acc"], ws.data_ptr(),
+                     n, C, *largs, src, 0 if acc_ro is None else acc_ro.data_ptr(), REP_DENSE, sws,
+                     0 if self.loss_sum is None else self.loss_sum.data_ptr(), _stream()),
+               name)
         st["djk"] = djk
         return loss, logits
 
@@ -945,7 +950,7 @@ def _one(device):
 
 def step_supported(model, loss_fn):
     """True when `model` (models.GLASS) + loss can run as StackProgram.loss_and_grads: one feature channel, the stack
-    program's own conditions, pooling sum|mean|size straight from the padded node matrix, a bare Linear head whose
+    program's own conditions, pooling sum|mean|size|max straight from the padded node matrix, a bare Linear head whose
     gradients live in the arena, a fusable loss."""
     import torch.nn as nn
     from . import losses
@@ -954,14 +959,18 @@ def step_supported(model, loss_fn):
     if not (USE_READOUT and isinstance(emb, EmbZGConv) and StackProgram.supported(emb) and emb.training):
         return False
     pool, head = model.pools[0], model.preds[0]
-    if not (isinstance(pool, PoolModule) and pool.trans_fn is None and pool.mode in ("sum", "mean", "size")):
+    if not (isinstance(pool, PoolModule) and pool.trans_fn is None and pool.mode in ("sum", "mean", "size", "max")):
         return False
     if not (type(head) is nn.Linear and head.bias is not None and head.weight.grad is not None and
             head.bias.grad is not None and losses.fusable_mode(loss_fn) is not None):
         return False
     C = emb.gns[-1].weight.shape[0]
-    return head.weight.shape[1] == C and bool(_lib.load().glass_readout_supported(C, head.weight.shape[0],
-                                                                                  _lib.POOL_MODES[pool.mode]))
+    lib, K = _lib.load(), head.weight.shape[0]
+    if head.weight.shape[1] != C:
+        return False
+    if pool.mode == "max":
+        return bool(lib.glass_readout_max_supported(C, K))
+    return bool(lib.glass_readout_supported(C, K, _lib.POOL_MODES[pool.mode]))
 
 
 def covers_arena(model, arena):

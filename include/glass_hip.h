@@ -729,6 +729,27 @@ int glass_readout_train_f32(const float* jk, int64_t ldj, const float* gn_saved,
  *      the caller per step, gn_bwd_rep replicas in use), the backfill launch folds them and also carries the head-gradient
  *      rows and the mean loss. */
 
+/* K8r (max)  the same training-step readout with MaxPool (GLASSTest.py:162-167 `pool_fn_fn`, impl/models.py:300-303
+ *      MaxPool = global_max_pool, applied by impl/models.py:346-350 to the GraphNorm OUTPUT y = gamma * xhat + beta; gamma may
+ *      be negative, so the max is over y).  Semantics of glass_segment_pool_f32's max mode: per subgraph and column the max
+ *      over the valid entries of the row of pos; strict compare, on a tie the LOWEST position in the row wins (a node listed
+ *      twice counts at its first position); padding / out-of-range ids skipped; an empty row pools to 0 and gets no gradient.
+ *      Same launches, same optional forms (lab_rows, gn_src, gn_bwd_acc, scatter_ws, loss_sum), same host-side checks and
+ *      the same promise as glass_readout_train_f32: no float atomics, bitwise repeatable, GLASS_E_WS without scatter_ws
+ *      beyond 16 384 padded entries.  The argument list is glass_readout_train_f32's without pool_mode.  The workspace is
+ *      that entry's layout followed by the [B][C] int32 argmax positions (glass_readout_max_ws_bytes); C and K limits as
+ *      glass_readout_supported.  glass_readout_supported / glass_readout_train_f32 keep refusing GLASS_POOL_MAX. */
+int glass_readout_max_supported(int64_t C, int64_t K);                    /* GLASSTest.py:162-167 (pool: max) */
+int64_t glass_readout_max_ws_bytes(int64_t B, int64_t C, int64_t K);      /* impl/models.py:300-303: + argmax [B][C] */
+int glass_readout_max_train_f32(const float* jk, int64_t ldj, const float* gn_saved, const float* gamma, const float* alpha,
+                                const int64_t* pos, int64_t B, int64_t Smax, const float* Wh, const float* bh,
+                                const void* target, int loss_mode, int64_t K, const float* grad_loss, float* pooled,
+                                float* logits, float* loss, float* djk, int64_t lddj, float* dWh, float* dbh, int acc_head,
+                                float* dgamma, float* dbeta, float* dalpha, int acc_gn, void* ws, int64_t n_nodes, int64_t C,
+                                const uint8_t* mask, const int32_t* lab_rows, const int32_t* lab_count,
+                                const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
+                                float* loss_sum, void* stream);           /* impl/models.py:300-303, 346-350 */
+
 /*     Two small device-to-device copies in one launch (4-byte granularity): a training step that is replayed from a
  *     captured graph reads its batch (pos, target) from fixed buffers; this fills both per step. */
 int glass_copy_pair(void* dst0, const void* src0, int64_t bytes0, void* dst1, const void* src1, int64_t bytes1,
