@@ -138,9 +138,12 @@ def segment_pool(emb, batch, n_seg, mode):
 # ----------------------------------------------------------------------------------------
 # model                                                   (reference impl/models.py:114-355)
 # ----------------------------------------------------------------------------------------
-# Dropout (models.py:166, 251, 259: F.dropout with the YAML's p).  A test may FEED the masks: `mask_feed(list)` makes the
-# next dropouts, in call order, multiply by the given keep-scale tensors (0 or 1/(1-p)) instead of drawing their own — how
-# a dropout-on run of the HIP path is compared with this restatement on the very same masks.
+# Dropout (models.py:166, 251, 259; on the pre-training path EmbGConv.forward's two F.dropout calls and the MLP head's
+# nn.Dropout; all with the YAML's p).  The call order on the pre-training path is: the embedding, behind each non-last
+# layer's ReLU, the head.
+# A test may FEED the masks: `mask_feed(list)` makes the next dropouts, in call order, multiply by the given keep-scale
+# tensors (0 or 1/(1-p)) instead of drawing their own — how a dropout-on run of the HIP path is compared with this
+# restatement on the very same masks.
 _MASK_FEED = []
 
 
@@ -302,12 +305,12 @@ class OracleEmbGConv(nn.Module):
 
     def forward(self, x, edge_index, edge_weight, z=None):
         act = _relu  # GNNEmb.py:90 nn.ReLU(inplace=True)  (F.relu unless a test feeds derivative masks)
-        h = F.dropout(self.input_emb(x.reshape(-1)), p=self.dropout, training=self.training)
+        h = _dropout(self.input_emb(x.reshape(-1)), self.dropout, self.training)
         saved = []
         for l, conv in enumerate(self.convs[:-1]):
             h = act(self.gns[l](conv(h, edge_index, edge_weight, act)))  # in-place ReLU aliases the saved tensor
             saved.append(h)
-            h = F.dropout(h, p=self.dropout, training=self.training)
+            h = _dropout(h, self.dropout, self.training)
         saved.append(self.convs[-1](h, edge_index, edge_weight, act))
         return torch.cat(saved, dim=-1) if self.jk else saved[-1]
 
@@ -329,10 +332,14 @@ class OracleEdgeGNN(nn.Module):
             def forward(self, h):
                 return _relu(h)
 
+        class _Dropout(nn.Module):  # nn.Dropout(dropout) of the reference's MLP (no parameters: the same keys), feedable
+            def forward(self, h):
+                return _dropout(h, dropout, self.training)
+
         class _MLP(nn.Module):
             def __init__(self):
                 super().__init__()
-                mods = [nn.Linear(width, hidden)] + ([nn.Dropout(dropout)] if dropout > 0 else []) + \
+                mods = [nn.Linear(width, hidden)] + ([_Dropout()] if dropout > 0 else []) + \
                        [_ReLU(), nn.Linear(hidden, 1)]
                 self.seq = _Seq(mods)
 

@@ -24,13 +24,18 @@ def _build(h, layers, max_deg, aggr, dropout=0.0, act=None):
     return models.EdgeGNN(conv, nn.ModuleList([head]), nn.ModuleList([models.MeanPool()]))
 
 
-def _oracle(sd, h, layers, max_deg, aggr, x, ei, ew, pairs, y, dt, relu_masks=None):
-    orc = O.OracleEdgeGNN(h, layers, max_deg, aggr=aggr, jk=False)
+def _oracle(sd, h, layers, max_deg, aggr, x, ei, ew, pairs, y, dt, relu_masks=None, dropout=0.0, scales=None):
+    orc = O.OracleEdgeGNN(h, layers, max_deg, aggr=aggr, dropout=dropout, jk=False)
     orc.load_state_dict(sd)
     orc = orc.to(dt).train()
     O.relu_mask_feed(relu_masks or [])
-    po = orc(x, ei, ew.to(dt), pairs)
-    O.relu_mask_feed([])
+    O.mask_feed(scales or [])
+    try:
+        po = orc(x, ei, ew.to(dt), pairs)
+        assert not O._RELU_FEED and not O._MASK_FEED  # every fed mask was consumed, in order
+    finally:
+        O.relu_mask_feed([])
+        O.mask_feed([])
     lo = nn.BCEWithLogitsLoss()(po.flatten(), y.to(dt))
     lo.backward()
     return po.detach(), lo.item(), {k: p.grad for k, p in orc.named_parameters()}
@@ -96,6 +101,93 @@ def test_pair_program_vs_oracle(layers, aggr, n_pairs, features):
     assert float(c0._stack["trans"][0][:h].abs().max()) == 0.0 and float(c0._stack["trans"][2][:h].abs().max()) == 0.0
     # evaluation forward of the program = the training forward's logits (dropout 0)
     assert rel_inf(prog.predict(x.to(DEV), ei.to(DEV), ew.to(DEV), pairs.to(DEV)).cpu().flatten(), pred) < 1e-6
+
+
+@pytest.mark.parametrize("layers,aggr", [(2, "mean"), (3, "gcn"), (1, "sum")])
+def test_pair_program_dropout_vs_oracle_on_the_same_masks(layers, aggr):
+    """The pre-training step WITH dropout 0.5 (the driver's search space, GNNEmb.py:171) against the fp64 oracle given the
+    very masks the kernels drew (glass_dropout_scales_f32 on the pass's (seed, step) words): stream 1 for the embedding,
+    16 (l + 1) + 1 behind each non-last layer's ReLU, 2 for the head — the oracle's call order — and on the same ReLU
+    branches (a dropped element has h = 0 and scale 0: the two feeds agree).  Small random graph (1503 nodes, 20 000
+    directed edges, degree features capped at 15), 4097 pairs with a hub; plain 1e-5 bar on logits, loss and every gradient."""
+    from glass_amd import synth, ssl, ops, _lib
+    from glass_amd.arena import ParamArena
+    n, h, P, p = 1503, 64, 4097, 0.5
+    ei, ew = synth.make_graph(n, 10000, 4 + layers, 0.0)
+    x = np.minimum(synth.degree_feature(ei, n), 15)
+    rng = np.random.default_rng(30 + layers)
+    pairs = rng.integers(0, n, size=(P, 2))
+    pairs[:150, 0] = 7
+    pairs = torch.from_numpy(pairs)
+    y = torch.from_numpy(rng.integers(0, 2, size=P).astype(np.float32))
+    ei, ew, x = (torch.from_numpy(a) for a in (ei, ew, x))
+    torch.manual_seed(40 + layers)
+    model = _build(h, layers, int(x.max()), aggr, dropout=p)
+    sd = {k: v.clone() for k, v in model.state_dict().items()}
+    model.to(DEV).train()
+    arena = ParamArena(model)
+    prog = ssl.program_for(model)
+    assert prog is not None and prog.covers_arena() and prog.p_head == p
+    arena.flat.fill_(7.0)
+    ops.rng_seed(2025 + layers, DEV)
+    loss = prog.loss_and_grads(x.to(DEV), ei.to(DEV), ew.to(DEV), pairs.to(DEV), y.to(DEV))
+    torch.cuda.synchronize()
+    mine = {k: q.grad.cpu().clone() for k, q in model.named_parameters()}
+    pred, hid = prog.last["logits"].cpu(), prog.last["hid"].cpu()
+
+    def scales(call_id, rows):
+        m = torch.empty(rows, h, device=DEV)
+        _lib.check(_lib.load().glass_dropout_scales_f32(ops.rng_state(DEV).data_ptr(), call_id, p, rows, h, m.data_ptr(),
+                                                        torch.cuda.current_stream().cuda_stream), "glass_dropout_scales_f32")
+        m = m.cpu()
+        assert set(m.unique().tolist()) == {0.0, 2.0} and abs(float((m > 0).double().mean()) - 0.5) < 0.02
+        return m
+    feed = [scales(1, n)] + [scales(16 * (l + 1) + 1, n) for l in range(layers - 1)] + [scales(2, P)]
+    assert all(not torch.equal(feed[i], feed[j]) for i in range(layers) for j in range(i))  # every stream its own masks
+    assert bool((hid[feed[-1] == 0] == 0).all())
+    # the layer-0 input the program kept = dropout(input_emb(x)): table row x scale, to fp32 rounding
+    h0 = prog.last["layers"][0]["h"].cpu()
+    assert rel_inf(h0, sd["conv.input_emb.weight"][x.reshape(-1)].double() * feed[0].double()) < 1e-6
+    assert bool((h0[feed[0] == 0] == 0).all())
+    masks = _program_masks(prog, h)
+    assert len(masks) == 2 * layers
+    po, lo, theirs = _oracle(sd, h, layers, int(x.max()), aggr, x, ei, ew, pairs, y, torch.float64, masks, dropout=p, scales=feed)
+    keys = sorted(mine)
+    assert keys == sorted(theirs)
+    e_pred, e_loss = rel_inf(pred, po.flatten()), abs(loss.item() - lo) / abs(lo)
+    e_grad = rel_inf(flat_grads(mine, keys), flat_grads(theirs, keys))
+    print(f"pair program dropout {p} L={layers} {aggr}: pred {e_pred:.2e} loss {e_loss:.2e} grad {e_grad:.2e}")
+    record_parity(f"pair_program_dropout_same_masks/L{layers}_{aggr}", pred_rel_inf=e_pred, loss_rel=e_loss, grad_rel_inf=e_grad)
+    assert e_pred < TOL and e_loss < TOL and e_grad < TOL
+
+
+def test_pair_program_per_op_path_vs_the_oracle_with_an_empty_feed(monkeypatch):
+    """The per-op path of the same model (hidden 8 is not the program's width; the stack switched off as well) at dropout 0
+    against the oracle whose dropouts now go through the feedable helper: with nothing fed the oracle is the one the
+    reference-run fixture g10 pins, and the per-op path's predictions, loss and gradients match both."""
+    from glass_amd import ssl, models
+    from glass_amd.arena import ParamArena
+    monkeypatch.setattr(models, "USE_STACK", False)
+    g = load("g10_edgegnn_L2_jk0_mean.npz")
+    x, ei, ew, pairs, y = (torch.from_numpy(g[k]) for k in ("x", "edge_index", "edge_weight", "pairs", "y"))
+    hdim = int(g["hidden"])
+    model = _build(hdim, 2, int(x.max()), "mean")
+    model.load_state_dict(sd_from(g))
+    model.to(DEV).train()
+    ParamArena(model)
+    assert ssl.program_for(model) is None
+    pred = model(x.to(DEV), ei.to(DEV), ew.to(DEV), pairs.to(DEV))
+    loss = nn.BCEWithLogitsLoss()(pred.flatten(), y.to(DEV))
+    loss.backward()
+    mine = {k: q.grad.cpu() for k, q in model.named_parameters()}
+    assert not O._MASK_FEED and not O._RELU_FEED
+    po, lo, theirs = _oracle(sd_from(g), hdim, 2, int(x.max()), "mean", x, ei, ew, pairs, y, torch.float64)
+    ref = grads_from(g, "grad64/")
+    keys = sorted(ref)
+    assert sorted(mine) == keys == sorted(theirs)
+    assert rel_inf(po, g["pred64"]) < 1e-11 and rel_inf(flat_grads(theirs, keys), flat_grads(ref, keys)) < 1e-11
+    assert rel_inf(pred.detach().cpu(), po) < TOL and abs(loss.item() - lo) < TOL * abs(lo)
+    assert rel_inf(flat_grads(mine, keys), flat_grads(theirs, keys)) < TOL
 
 
 def test_pair_program_g10_golden_shape_is_served_by_the_per_op_path():

@@ -219,6 +219,62 @@ def test_g10_edgegnn_ssl_path(name):
         assert rel_inf(flat_grads(mine, keys), flat_grads(ref, keys)) < tol
 
 
+@pytest.mark.parametrize("name,p", [("L2_jk0_mean", 0.5), ("L3_jk1_gcn", 0.3), ("L1_jk0_sum", 0.5)])
+def test_edgegnn_fed_dropout_masks_reproduce_the_unfed_run(name, p, monkeypatch):
+    """The pre-training oracle takes fed keep-scales (O.mask_feed) at all of its dropouts — the embedding, behind each
+    non-last layer's ReLU, the head, in that order: feeding the scales F.dropout itself draws under a seed reproduces the
+    unfed fp64 forward and gradients bit for bit, and the feed is used up.  The scales are recorded by a hook around
+    O._dropout that replays the draw of each call on a tensor of ones."""
+    g = load(f"g10_edgegnn_{name}.npz")
+    x, ei, ew = torch.from_numpy(g["x"]), torch.from_numpy(g["edge_index"]), torch.from_numpy(g["edge_weight"])
+    pairs, y = torch.from_numpy(g["pairs"]), torch.from_numpy(g["y"])
+    layers = int(g["layers"])
+    torch.manual_seed(11)
+    m = O.OracleEdgeGNN(int(g["hidden"]), layers, int(x.max()), aggr=str(g["aggr"]), dropout=p, jk=bool(g["jk"])).double().train()
+    keys = sorted(k for k, _ in m.named_parameters())
+    assert "preds.0.seq.modlist.0.weight" in keys and "preds.0.seq.modlist.3.weight" in keys  # the reference's keys at p > 0
+
+    def run():
+        m.zero_grad()
+        pred = m(x, ei, ew.double(), pairs)
+        loss = nn.BCEWithLogitsLoss()(pred.flatten(), y.double())
+        loss.backward()
+        return pred.detach().clone(), loss.item(), flat_grads({k: q.grad for k, q in m.named_parameters()}, keys).clone()
+
+    recorded, plain = [], O._dropout
+
+    def recording(h, pp, training):
+        state = torch.get_rng_state()
+        out = plain(h, pp, training)
+        after = torch.get_rng_state()
+        torch.set_rng_state(state)
+        recorded.append(torch.nn.functional.dropout(torch.ones_like(h), p=pp, training=training))
+        assert torch.equal(torch.get_rng_state(), after)  # the replay consumed what the call consumed
+        return out
+
+    O.mask_feed([])
+    monkeypatch.setattr(O, "_dropout", recording)
+    torch.manual_seed(5)
+    pred0, loss0, grad0 = run()
+    monkeypatch.setattr(O, "_dropout", plain)
+    torch.manual_seed(5)
+    pred1, loss1, grad1 = run()  # unfed, unhooked: the hook changed nothing
+    assert torch.equal(pred0, pred1) and loss0 == loss1 and torch.equal(grad0, grad1)
+    assert len(recorded) == 1 + (layers - 1) + 1
+    assert [tuple(r.shape) for r in recorded] == [(x.shape[0], int(g["hidden"]))] * layers + [(pairs.shape[0], int(g["hidden"]))]
+    for r in recorded:
+        assert set(r.unique().tolist()) == {0.0, 1.0 / (1.0 - p)}
+    torch.manual_seed(77)  # another seed: a fed run draws nothing
+    O.mask_feed(recorded)
+    try:
+        pred2, loss2, grad2 = run()
+        assert not O._MASK_FEED  # fully consumed, in call order
+    finally:
+        O.mask_feed([])
+    assert torch.equal(pred2, pred0) and loss2 == loss0 and torch.equal(grad2, grad0)
+    assert float(grad0.abs().max()) > 0 and not torch.equal(run()[0], pred0)  # (unfed again under seed 77's stream: other masks)
+
+
 G11 = ["relu_gn_max_mean", "relu_nogn_sum_gcn", "relu_gn_size_sum"]
 
 
