@@ -21,7 +21,7 @@ from torch.nn import BCEWithLogitsLoss, CrossEntropyLoss
 from torch.optim import Adam, lr_scheduler
 
 import datasets
-from glass_amd import seg
+from glass_amd import ops, seg
 from impl import config, metrics, models, train
 
 DEGREE_FEATURE_SETS = ("hpo_metab", "hpo_neuro", "ppi_bp", "em_user")
@@ -71,6 +71,10 @@ def set_seed(seed: int):
     torch.manual_seed(seed)
     torch.cuda.manual_seed(seed)
     torch.cuda.manual_seed_all(seed)
+    if torch.cuda.is_available():
+        # the head's dropout masks come from the device-resident stream (losses.mlp_head_loss): a repeat stays a function of its seed
+        on_gpu = config.device is not None and config.device.type == "cuda"
+        ops.rng_seed(seed, config.device if on_gpu else "cuda")
 
 
 class Run:

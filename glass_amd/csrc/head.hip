@@ -5,14 +5,9 @@
 // The operands are tiny (B ~ 80 subgraphs, C = H*L = 128 features, K <= ~50 classes) but as separate
 // library calls they are ~12 launches of ~4 us each (GEMM, softmax, nll, fills, three backward GEMMs,
 // bias reduction, gradient accumulations): pure launch latency on this path.
-#include "common.h"
+#include "head_loss.h"
 
 namespace glass {
-
-constexpr int GLASS_LOSS_CE = 0;
-constexpr int GLASS_LOSS_BCE = 1;
-
-constexpr int kMaxK = 256;  // classes handled by the per-subgraph workgroup
 
 // One workgroup per subgraph b: its pooled row is staged in LDS, each wave computes logits[b,k] for
 // k = wave, wave+4, ... as a 64-lane dot product (one round trip to memory), then lane 0 of wave 0 does the
@@ -36,30 +31,7 @@ __global__ __launch_bounds__(kBlock) void head_logits_kernel(const float* __rest
     }
     __syncthreads();
     if (threadIdx.x != 0) return;
-    float term = 0.f;
-    if (mode == GLASS_LOSS_CE) {
-        float m = zs[0];
-        for (int k = 1; k < K; ++k) m = fmaxf(m, zs[k]);
-        float se = 0.f;
-        for (int k = 0; k < K; ++k) se += expf(zs[k] - m);
-        const float lse = m + logf(se);
-        for (int k = 0; k < K; ++k) {
-            logits[(int64_t)b * K + k] = zs[k];
-            prob[(int64_t)b * K + k] = expf(zs[k] - lse);
-        }
-        const int64_t t = ((const int64_t*)target)[b];
-        term = (t >= 0 && t < K) ? lse - zs[t] : 0.f;
-    } else {
-        const float* y = (const float*)target + (int64_t)b * K;
-        for (int k = 0; k < K; ++k) {
-            const float z = zs[k];
-            logits[(int64_t)b * K + k] = z;
-            prob[(int64_t)b * K + k] = 1.f / (1.f + expf(-z));
-            // max(z,0) - z*y + log(1 + exp(-|z|))   (torch's stable BCE-with-logits)
-            term += fmaxf(z, 0.f) - z * y[k] + log1pf(expf(-fabsf(z)));
-        }
-    }
-    loss_rows[b] = term;
+    loss_rows[b] = head_loss_row(zs, target, mode, b, K, logits, K, prob);
 }
 
 // The head alone (evaluation: no target, no loss): logits[b, k] = pooled[b, :] . W[k, :] + bias[k], one wave per (b, k) pair
@@ -81,22 +53,7 @@ __global__ __launch_bounds__(kBlock) void head_linear_kernel(const float* __rest
 
 __global__ __launch_bounds__(kBlock) void head_loss_mean_kernel(const float* __restrict__ loss_rows, int B, float denom,
                                                                 float* __restrict__ loss) {
-    __shared__ double red[kBlock];
-    double part = 0.0;
-    for (int b = threadIdx.x; b < B; b += kBlock) part += (double)loss_rows[b];
-    red[threadIdx.x] = part;
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)denom);
-}
-
-__device__ __forceinline__ float dlogit(const float* prob, const void* target, int mode, int b, int k, int K, float scale) {
-    const float p = prob[(int64_t)b * K + k];
-    if (mode == GLASS_LOSS_CE) return scale * (p - (((const int64_t*)target)[b] == k ? 1.f : 0.f));
-    return scale * (p - ((const float*)target)[(int64_t)b * K + k]);
+    head_loss_mean(loss_rows, B, denom, loss);
 }
 
 // Workgroups 0..B-1: dpooled[b,:] = dlogits[b,:] @ W.   Workgroups B..B+K-1: dW[k,:] (+)= sum_b dlogits[b,k] *

@@ -4,7 +4,10 @@
 (GLASSTest.py:57-58, 69) when called as `loss_fn(pred, y)`; in addition `glass_amd.step.TrainStep`
 recognises them — and any callable that computes one of them, the reference driver's own lambda included (`fusable_mode`) —
 and, when the model's head is a bare nn.Linear (GLASSTest.py:159-160), runs head + loss + their backward as two kernels
-(`glass_head_loss_fwd/bwd_f32`) instead of ~12 launches."""
+(`glass_head_loss_fwd/bwd_f32`) instead of ~12 launches.  The reference's other head, the two-layer `models.MLP` of GNN-seg
+and GNNEmb (Linear -> Dropout -> activation -> Linear), is recognised by `fusable_head` and runs with its loss and their
+backward as four launches (`mlp_head_loss`, `glass_head_mlp_loss_fwd/bwd_f32`); DESIGN.md has the launch counts measured
+with and without it."""
 import torch
 import torch.nn as nn
 
@@ -159,3 +162,138 @@ class HeadLossFn(torch.autograd.Function):
 def head_loss(pooled, linear, target, mode, direct=False):
     """-> (loss, logits) for an nn.Linear head; mode 0 = cross-entropy, 1 = BCE-with-logits."""
     return HeadLossFn.apply(pooled, linear.weight, linear.bias, target, mode, direct)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The two-layer MLP head: MLP(in, hidden, out, 2, dropout, activation) = Linear -> Dropout -> activation -> Linear
+# (reference impl/models.py:56-80), the head of GNN-seg (GNNSeg.py:272-277) and of GNNEmb.
+# ---------------------------------------------------------------------------------------------------------------------
+# Dropout streams (`call_id`) of the device-resident generator: 1 the embedding's GraphNorm, 2 the pair head (ssl.py),
+# 16 (l + 1) [+ 1] the GraphNorm dropouts of conv layer l (models.EmbZGConv / EmbGConv) — and 3 this head's.
+HEAD_MLP_CALL_ID = 3
+
+
+def _mlp2_parts(pred):
+    """(first Linear, dropout p, activation code, second Linear) of a fusable two-layer models.MLP, else None."""
+    from .models import MLP, _act_code
+    if type(pred) is not MLP:
+        return None
+    mods = list(pred.seq.modlist)
+    p = 0.0
+    if len(mods) == 4 and type(mods[1]) is nn.Dropout:  # (dropout == 0 builds no Dropout module: the Linear is modlist.2)
+        p = float(mods[1].p)
+        del mods[1]
+    if len(mods) != 3 or not 0.0 <= p < 1.0:
+        return None
+    lin1, act, lin2 = mods
+    code = _act_code(act)
+    if not (isinstance(lin1, nn.Linear) and isinstance(lin2, nn.Linear) and lin1.bias is not None and
+            lin2.bias is not None and code is not None and lin2.in_features == lin1.out_features):
+        return None
+    return lin1, p, code, lin2
+
+
+def fusable_head(pred):
+    """"linear": a bare nn.Linear with bias (GLASSTest.py:159-160) — head_loss; "mlp2": a models.MLP whose sequence is
+    exactly [Linear, (Dropout)?, ELU | ReLU, Linear], both Linears with bias (no GraphNorm, no tail activation) —
+    mlp_head_loss; None: anything else runs as the module."""
+    if type(pred) is nn.Linear and pred.bias is not None:
+        return "linear"
+    return "mlp2" if _mlp2_parts(pred) is not None else None
+
+
+class _HeadUnsupported(Exception):
+    """The C entry refused the sizes (GLASS_E_UNSUPPORTED) before any launch: the caller runs the modules."""
+
+
+class MLPHeadLossFn(torch.autograd.Function):
+    """loss = L(act(dropout(pooled @ W1^T + b1)) @ W2^T + b2, target) — forward in two launches, backward in two.
+    rng: the (seed, step) words this call's dropout reads, in the forward and again in the backward (None: no dropout)."""
+    @staticmethod
+    def forward(ctx, pooled, w1, b1, w2, b2, target, mode, act, p_drop, rng, direct):
+        ops._need_gpu(pooled, w1, w2, target)
+        pooled, ldp = ops._rows(pooled)
+        B, C = pooled.shape
+        Hd, K = w1.shape[0], w2.shape[0]
+        if w1.shape[1] != C or w2.shape[1] != Hd or any(t.dtype != torch.float32 for t in (w1, b1, w2, b2)):
+            raise _lib.GlassHipError(f"MLP head: fp32 weights [Hd,{C}] and [K,Hd] expected, got {tuple(w1.shape)} {w1.dtype}, "
+                                     f"{tuple(w2.shape)} {w2.dtype}")
+        params = (w1, b1, w2, b2)
+        w1c, b1c, w2c, b2c = (t.contiguous() for t in params)
+        tgt = target.contiguous().to(torch.int64 if mode == 0 else torch.float32)
+        dev = pooled.device
+        hidden = torch.empty((B, Hd), dtype=torch.float32, device=dev)
+        logits = torch.empty((B, K), dtype=torch.float32, device=dev)
+        prob = torch.empty(B * K + B, dtype=torch.float32, device=dev)  # probabilities + per-row loss terms
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        rc = _lib.load().glass_head_mlp_loss_fwd_f32(pooled.data_ptr(), ldp, w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(),
+                                                     b2c.data_ptr(), tgt.data_ptr(), mode, act, p_drop,
+                                                     0 if rng is None else rng.data_ptr(), HEAD_MLP_CALL_ID, B, C, Hd, K,
+                                                     hidden.data_ptr(), logits.data_ptr(), prob.data_ptr(), loss.data_ptr(),
+                                                     ops._stream())
+        if rc == -3:  # GLASS_E_UNSUPPORTED
+            raise _HeadUnsupported(_lib.load().glass_last_error_string().decode(errors="replace"))
+        _lib.check(rc, "glass_head_mlp_loss_fwd_f32")
+        ctx.save_for_backward(pooled, w1c, w2c, hidden, prob, tgt)
+        ctx.cfg = (mode, act, p_drop, B, C, Hd, K, ldp)
+        ctx.rng = rng
+        # direct: accumulate the four gradients straight into the flat gradient arena (the parameters' .grad views)
+        ctx.direct = params if (direct and all(t.grad is not None for t in params)) else None
+        ctx.mark_non_differentiable(logits)
+        ctx.set_materialize_grads(False)  # no zero-filled gradient tensor for the logits output
+        return loss, logits
+
+    @staticmethod
+    def backward(ctx, gl, _glogits):
+        pooled, w1, w2, hidden, prob, tgt = ctx.saved_tensors
+        mode, act, p_drop, B, C, Hd, K, ldp = ctx.cfg
+        gl = gl.contiguous().reshape(1).to(torch.float32)
+        dev = pooled.device
+        dpooled = torch.empty((B, C), dtype=torch.float32, device=dev)
+        ws = torch.empty(2 * B * Hd, dtype=torch.float32, device=dev)
+        if ctx.direct is not None:
+            grads, acc = [t.grad for t in ctx.direct], 1
+        else:
+            grads, acc = [torch.empty_like(w1), torch.empty(Hd, dtype=torch.float32, device=dev), torch.empty_like(w2),
+                          torch.empty(K, dtype=torch.float32, device=dev)], 0
+        rc = _lib.load().glass_head_mlp_loss_bwd_f32(pooled.data_ptr(), ldp, w1.data_ptr(), w2.data_ptr(),
+                                                     hidden.data_ptr(), prob.data_ptr(), tgt.data_ptr(), mode, act, p_drop,
+                                                     0 if ctx.rng is None else ctx.rng.data_ptr(), HEAD_MLP_CALL_ID,
+                                                     gl.data_ptr(), B, C, Hd, K, ws.data_ptr(), dpooled.data_ptr(), C,
+                                                     *(g.data_ptr() for g in grads), acc, ops._stream())
+        _lib.check(rc, "glass_head_mlp_loss_bwd_f32")
+        if ctx.direct is not None:
+            return (dpooled, ) + (None, ) * 10
+        return (dpooled, *grads) + (None, ) * 6
+
+
+def mlp_head_loss(pooled, mlp, target, mode, direct=False):
+    """-> (loss, logits) for a two-layer models.MLP head (fusable_head(mlp) == "mlp2"); mode 0 = cross-entropy, 1 =
+    BCE-with-logits.  In training with dropout the mask comes from the device-resident counter stream (stream
+    HEAD_MLP_CALL_ID): this call reads a private snapshot of the (seed, step) words, in its forward and in its backward, and
+    advances the live stream — a later training forward cannot pair this backward with another mask.  Same distribution as
+    nn.Dropout's, other bits.  Sizes the kernels refuse (GLASS_E_UNSUPPORTED: more than 256 classes or 1024 hidden units) run
+    as the modules, same semantics; so do tensors that are not fp32 on the GPU."""
+    lin1, p, act, lin2 = _mlp2_parts(mlp)
+    p = p if mlp.training else 0.0
+
+    def modules():
+        logits = mlp(pooled)
+        if mode == 0:
+            return nn.functional.cross_entropy(logits, target), logits
+        return nn.functional.binary_cross_entropy_with_logits(logits.flatten(), target.flatten().to(logits.dtype)), logits
+
+    params = (lin1.weight, lin1.bias, lin2.weight, lin2.bias)
+    # the kernels are fp32 on the GPU: anything else (a half / double model, a CPU tensor) is the modules' business, as before
+    if not (pooled.is_cuda and pooled.dim() == 2 and all(t.dtype == torch.float32 and t.is_cuda for t in (pooled, ) + params)):
+        return modules()
+    # the words are copied BEFORE the stream advances, and it advances only after the entry accepted the call: a refused call
+    # leaves the stream alone.  (The first mask after ops.rng_seed is therefore drawn at step word 0.)
+    rng = ops.rng_snapshot(pooled.device) if p > 0 else None
+    try:
+        out = MLPHeadLossFn.apply(pooled, *params, target, mode, act, p, rng, direct)
+    except _HeadUnsupported:
+        return modules()
+    if rng is not None:
+        ops.rng_advance(pooled.device)  # the next training forward draws another mask
+    return out

@@ -81,7 +81,8 @@ class Linear(nn.Linear):
 
 class MLP(nn.Module):
     """Linear / GraphNorm / Dropout / activation stack with the reference's layer ordering
-    (only GNNEmb / GNNSeg use it; GLASSTest's head is a bare nn.Linear)."""
+    (GNNEmb / GNNSeg use it; GLASSTest's head is a bare nn.Linear).  The two-layer form without GraphNorm is the one
+    losses.fusable_head recognises ("mlp2"): losses.mlp_head_loss in training, _head below in evaluation."""
     def __init__(self, input_channels, hidden_channels, output_channels, num_layers, dropout=0, tail_activation=False,
                  activation=nn.ReLU(inplace=True), gn=False):
         super().__init__()
@@ -386,19 +387,37 @@ class GLASS(nn.Module):
 
 
 def _head(pred, emb):
-    """The prediction head.  A bare nn.Linear under no_grad (evaluation: train.test) runs as one small kernel of this
-    library (glass_head_linear_f32) instead of a library GEMM; anything else is the module itself."""
-    if (type(pred) is nn.Linear and not torch.is_grad_enabled() and emb.is_cuda and emb.dim() == 2 and
-            emb.dtype == torch.float32 and pred.weight.dtype == torch.float32):
-        from . import _lib
+    """The prediction head.  Under no_grad (evaluation: train.test) a bare nn.Linear runs as one small kernel of this
+    library (glass_head_linear_f32) instead of a library GEMM, and a two-layer MLP in eval mode (losses.fusable_head:
+    "mlp2", the GNN-seg / GNNEmb head) as one launch of glass_head_mlp_f32 instead of module by module; anything else is
+    the module itself."""
+    if (torch.is_grad_enabled() or not emb.is_cuda or emb.dim() != 2 or emb.dtype != torch.float32):
+        return pred(emb)
+    from . import _lib
+    stream = torch.cuda.current_stream().cuda_stream
+    if type(pred) is nn.Linear and pred.weight.dtype == torch.float32:
         emb = emb if emb.stride(1) == 1 else emb.contiguous()
         w = pred.weight if pred.weight.is_contiguous() else pred.weight.contiguous()
         out = torch.empty((emb.shape[0], w.shape[0]), dtype=torch.float32, device=emb.device)
         rc = _lib.load().glass_head_linear_f32(emb.data_ptr(), emb.stride(0), w.data_ptr(),
                                                0 if pred.bias is None else pred.bias.data_ptr(), emb.shape[0], emb.shape[1],
-                                               w.shape[0], out.data_ptr(), out.stride(0), torch.cuda.current_stream().cuda_stream)
+                                               w.shape[0], out.data_ptr(), out.stride(0), stream)
         _lib.check(rc, "glass_head_linear_f32")
         return out
+    if type(pred) is MLP and not pred.training and emb.shape[0] > 0:
+        from . import losses
+        parts = losses._mlp2_parts(pred)
+        if parts is not None and parts[0].weight.dtype == torch.float32 and parts[0].weight.shape[1] == emb.shape[1]:
+            lin1, _p, act, lin2 = parts
+            emb, ldp = ops._rows(emb)
+            w1, b1, w2, b2 = (t.contiguous() for t in (lin1.weight, lin1.bias, lin2.weight, lin2.bias))
+            out = torch.empty((emb.shape[0], w2.shape[0]), dtype=torch.float32, device=emb.device)
+            rc = _lib.load().glass_head_mlp_f32(emb.data_ptr(), ldp, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                                                act, emb.shape[0], emb.shape[1], w1.shape[0], w2.shape[0], out.data_ptr(),
+                                                out.stride(0), stream)
+            if rc != -3:  # (GLASS_E_UNSUPPORTED — sizes over the kernel's limits — runs the modules)
+                _lib.check(rc, "glass_head_mlp_f32")
+                return out
     return pred(emb)
 
 

@@ -30,7 +30,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .graph import CSROperand, _csr_from_sorted
-from .models import GraphNorm, _act_code
+from .models import GraphNorm, _act_code, _head
 
 
 def _stream():
@@ -433,9 +433,26 @@ class GNN(nn.Module):
         super().__init__()
         self.mods = nn.ModuleList([conv, pred])
 
-    def forward(self, x, edge_index, edge_weight, subG_node, id=0):
+    def _pooled(self, x, edge_index, edge_weight, subG_node):
         C = x.shape[1]
         embs = [self.mods[0](x[:, c, :].contiguous(), edge_index, edge_weight) for c in range(C)]
         emb = embs[0] if C == 1 else torch.stack(embs, dim=1).mean(dim=1)
-        emb = ops.segment_pool(emb, subG_node, "sum")
+        return ops.segment_pool(emb, subG_node, "sum")
+
+    def forward(self, x, edge_index, edge_weight, subG_node, id=0):
+        emb = self._pooled(x, edge_index, edge_weight, subG_node)
+        if not torch.is_grad_enabled() and not self.training:
+            return _head(self.mods[1], emb)  # evaluation: a two-layer MLP head in one launch
         return self.mods[1](emb)
+
+    def loss_and_logits(self, x, edge_index, edge_weight, subG_node, y, loss_fn):
+        """-> (loss, logits) of one batch: forward up to the pool, then head + loss as four launches forward and
+        backward (losses.mlp_head_loss) when the loss is cross-entropy / BCE-with-logits (losses.fusable_mode) and the
+        head a two-layer MLP (losses.fusable_head); otherwise the head module and loss_fn(logits, y)."""
+        from . import losses
+        emb = self._pooled(x, edge_index, edge_weight, subG_node)
+        mode = losses.fusable_mode(loss_fn)
+        if mode is not None and losses.fusable_head(self.mods[1]) == "mlp2":
+            return losses.mlp_head_loss(emb, self.mods[1], y, mode)
+        logits = self.mods[1](emb)
+        return loss_fn(logits, y), logits

@@ -71,15 +71,17 @@ class TrainStep:
 
     # -- the step body, split at the collective ---------------------------------------------------
     def _fused_head(self):
-        """Head + loss fusable: a bare nn.Linear head and one of glass_amd.losses' marker losses."""
-        import torch.nn as nn
+        """Head + loss fusable: "linear" (a bare nn.Linear head) or "mlp2" (a two-layer models.MLP, losses.fusable_head)
+        with a loss glass_amd.losses recognises; else None."""
         from . import losses
-        head = self.model.preds[0]
-        return losses.fusable_mode(self.loss_fn) is not None and type(head) is nn.Linear and head.bias is not None
+        if losses.fusable_mode(self.loss_fn) is None:
+            return None
+        return losses.fusable_head(self.model.preds[0])
 
     def _program_step(self):
         from . import stack
-        return (self._fused_head() and hasattr(self.bucket, "flat_param") and self.x.dim() == 3 and
+        # (the step program's fused readout holds the bare Linear head only: an MLP head runs the autograd form below)
+        return (self._fused_head() == "linear" and hasattr(self.bucket, "flat_param") and self.x.dim() == 3 and
                 self.x.shape[1:] == (1, 1) and stack.step_supported(self.model, self.loss_fn))
 
     def _fwd_bwd(self, tail_hook=None, apply_opt=False):
@@ -106,12 +108,14 @@ class TrainStep:
             raise RuntimeError("tail_hook needs the step program")
         z = utils.MaxZOZ(self.x, self._pos)
         self.bucket.zero()
-        if self._fused_head():
+        kind = self._fused_head()
+        if kind is not None:
             from . import losses
             emb = self.model.NodeEmb(self.x, self.ei, self.ew, z)
             pooled = self.model.Pool(emb, self._pos, self.model.pools[0])
-            loss, _logits = losses.head_loss(pooled, self.model.preds[0], self._y, losses.fusable_mode(self.loss_fn),
-                                             direct=hasattr(self.bucket, "flat_param"))
+            head_loss = losses.head_loss if kind == "linear" else losses.mlp_head_loss
+            loss, _logits = head_loss(pooled, self.model.preds[0], self._y, losses.fusable_mode(self.loss_fn),
+                                      direct=hasattr(self.bucket, "flat_param"))
         else:
             pred = self.model(self.x, self.ei, self.ew, self._pos, z, id=0)
             loss = self.loss_fn(pred, self._y)

@@ -97,13 +97,19 @@ def train(optimizer, model, dataloader, loss_fn):
         return out
     total_loss = []
     bucket = gdist.bucket_for(model) if gdist.is_distributed() else None
+    # (a loss that opts out of fusion — loss_fn._glass_no_fuse — is called as it is, once per step)
+    fused_head = hasattr(model, "loss_and_logits") and not getattr(loss_fn, "_glass_no_fuse", False)
     for batch in dataloader:
         if bucket is None:
             optimizer.zero_grad()
         else:
             bucket.zero()
-        pred = model(*batch[:-1], id=0)
-        loss = loss_fn(pred, batch[-1])
+        if fused_head:
+            # head + loss in one autograd node (GNN-seg: seg.GNN.loss_and_logits -> losses.mlp_head_loss)
+            loss, _pred = model.loss_and_logits(*batch[:-1], batch[-1], loss_fn)
+        else:
+            pred = model(*batch[:-1], id=0)
+            loss = loss_fn(pred, batch[-1])
         loss.backward()
         if bucket is not None:
             bucket.all_reduce_mean()

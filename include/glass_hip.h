@@ -693,6 +693,35 @@ int glass_head_loss_bwd_f32(const float* pooled, int64_t ldp, const float* W, co
 int glass_head_linear_f32(const float* pooled, int64_t ldp, const float* W, const float* bias, int64_t B, int64_t C, int64_t K,
                           float* logits, int64_t ldl, void* stream);
 
+/* K8m  the two-layer MLP head + loss: MLP(in, hidden, out, 2, dropout, activation) = Linear -> Dropout -> activation ->
+ *      Linear (layer order: impl/models.py:56-80; built for every dataset at GNNSeg.py:272-277), then the loss of K8 above.
+ *      fwd (2 launches): h = pooled[B,C] @ W1[Hd,C]^T + b1, a = act(h * keep), logits[B,K] = a @ W2[K,Hd]^T + b2; mode 0 =
+ *      cross-entropy (target int64[B]), 1 = BCE-with-logits on the flattened tensors (target float[B*K]), mean reduction.
+ *      keep = the inverted-dropout scales glass_dropout_scales_f32(rng_state, call_id, p_drop, B, Hd, ..) returns — drawn by
+ *      element (row, hidden unit), never stored: the backward regenerates them from the same words.  p_drop == 0 draws
+ *      nothing (rng_state may be NULL).  act: GLASS_ACT_NONE | _ELU | _RELU, evaluated with expm1f.  Written for the
+ *      backward: hidden_pre[B,Hd] (h before the dropout) and prob (float[B*K + B], as glass_head_loss_fwd_f32's).
+ *      bwd (2 launches): dlogits = grad_loss[0] * (prob - target) / (B or B*K); da = dlogits @ W2; dh = da * act'(h * keep)
+ *      * keep; dpooled[B,C] = dh @ W1 (row stride lddp); dW2 (+)= dlogits^T @ a, db2 (+)= colsum(dlogits), dW1 (+)= dh^T @
+ *      pooled, db1 (+)= colsum(dh): every sum over b in index order; accumulate != 0 adds into the four gradients (the flat
+ *      gradient arena), else overwrites.  ws: 2*B*Hd floats of uninitialised scratch.
+ *      glass_head_mlp_f32: the head alone for evaluation (no dropout, target or loss), one launch; the same sums in the
+ *      same order as the training entry, so bitwise its logits at p_drop == 0.
+ *      No float atomics, bitwise repeatable.  Any C (ldp >= C is honoured), K <= 256, Hd <= 1024, <= 21 KiB of LDS per
+ *      launch.  Checked on the host before any launch: null pointers and bad sizes -> GLASS_E_ARG; K or Hd over the limit,
+ *      an unknown mode or activation code -> GLASS_E_UNSUPPORTED (the caller runs the modules). */
+int glass_head_mlp_loss_fwd_f32(const float* pooled, int64_t ldp, const float* W1, const float* b1, const float* W2,
+                                const float* b2, const void* target, int mode, int act, float p_drop,
+                                const uint64_t* rng_state, uint64_t call_id, int64_t B, int64_t C, int64_t Hd, int64_t K,
+                                float* hidden_pre, float* logits, float* prob, float* loss, void* stream);
+int glass_head_mlp_loss_bwd_f32(const float* pooled, int64_t ldp, const float* W1, const float* W2, const float* hidden_pre,
+                                const float* prob, const void* target, int mode, int act, float p_drop,
+                                const uint64_t* rng_state, uint64_t call_id, const float* grad_loss, int64_t B, int64_t C,
+                                int64_t Hd, int64_t K, float* ws, float* dpooled, int64_t lddp, float* dW1, float* db1,
+                                float* dW2, float* db2, int accumulate, void* stream);
+int glass_head_mlp_f32(const float* pooled, int64_t ldp, const float* W1, const float* b1, const float* W2, const float* b2,
+                       int act, int64_t B, int64_t C, int64_t Hd, int64_t K, float* logits, int64_t ldl, void* stream);
+
 /* K8r  training-step readout: final GraphNorm apply -> subgraph pooling -> Linear head -> loss AND the whole
  *      backward down to the gradient of the GraphNorm INPUT, in four launches (impl/models.py:266/271, 346-350;
  *      GLASSTest.py:159-160, 57-58/69).  Only pooled rows carry a gradient into the GraphNorm output, so its two
