@@ -25,6 +25,8 @@ SEG_MODES = {"gcn": 0, "gin": 1}  # GLASS_SEG_GCN / GLASS_SEG_GIN
 ACT_NONE, ACT_ELU, ACT_RELU = 0, 1, 2
 PLAN_HEADER_WORDS = 16
 EMBED_NORM_MAX_ROWS = 8192  # GLASS_EMBED_NORM_MAX_ROWS
+EVAL_F1_LANE_K = 16         # GLASS_EVAL_F1_LANE_K
+EVAL_MAX_K = 256            # columns the evaluation-metric entries take (kMaxK)
 ABI_VERSION = 6
 
 
@@ -187,6 +189,9 @@ SIGNATURES = {
     "glass_seg_centre_index": (c_int, [_P, _P, _I, _I, _P, _P, _I, _P, _P]),
     "glass_seg_collate_centre": (c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P,
                                          _P, _P, _P, _I, _P, _P]),
+    "glass_eval_f1_counts_f32": (c_int, [_P, _I, _P, _I, _I, _I, c_int, _P, _P]),
+    "glass_eval_auroc_supported": (c_int, [_I, _I]),
+    "glass_eval_auroc_counts_f32": (c_int, [_P, _I, _P, _I, _I, _I, _P, _P]),
 }
 
 _lib = None

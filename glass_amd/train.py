@@ -121,6 +121,7 @@ def train(optimizer, model, dataloader, loss_fn):
 
 USE_EVAL_GRAPH = os.environ.get("GLASS_EVAL_GRAPH", "1") != "0"  # 0: one eager forward per evaluation batch
 EVAL_PARALLEL = int(os.environ.get("GLASS_EVAL_PARALLEL", "8"))   # evaluation batches run side by side (evalstep.EvalGraph)
+USE_EVAL_METRICS = os.environ.get("GLASS_EVAL_METRICS", "1") != "0"  # 0: the metric on the host, from a copy of pred and y
 
 
 EVAL_GRAPH_MAX_BYTES = int(os.environ.get("GLASS_EVAL_GRAPH_MAX_MB", "8192")) << 20  # activation budget of one cached graph
@@ -210,4 +211,10 @@ def test(model, dataloader, metrics, loss_fn):
             flush()
     flush()
     pred, y = torch.cat(preds, dim=0), torch.cat(ys, dim=0)
-    return metrics(pred.cpu().numpy(), y.cpu().numpy()), loss_fn(pred, y)
+    # the three metrics of glass_amd.metrics are counted on the GPU (exact integers; the counter read-back is the evaluation's
+    # one host sync); any other metric, and whatever the device path does not serve, sees host arrays as before
+    from . import metrics as metrics_module
+    score = metrics_module.device_score(metrics, pred, y) if USE_EVAL_METRICS else None
+    if score is None:
+        score = metrics(pred.cpu().numpy(), y.cpu().numpy())
+    return score, loss_fn(pred, y)

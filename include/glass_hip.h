@@ -893,6 +893,39 @@ int glass_seg_collate_centre(const int32_t* sub_ptr, const int32_t* sub_nodes, i
                              int32_t* bcol_in, float* bval_in, int32_t* bcol_out, float* bval_out,
                              int32_t* node_map, int64_t* pos, int64_t pos_width, uint8_t* mark, void* stream);
 
+/* K11 evaluation metrics from exact integer counts: the GPU counts, the host divides (glass_amd/metrics.py).  Integer
+ *     sums only — ballot + popcount per wave, one integer atomic add per wave and counter — so every counter is
+ *     independent of the order of arrival: bitwise repeatable, no float atomics.  fp32 predictions with a row stride
+ *     ld >= K in elements.  Each entry zeroes `counts` itself on `stream` (a fill launch in front of the counting
+ *     launch: two kernel nodes under capture), allocates nothing and does not synchronise.
+ *     glass_eval_f1_counts_f32: counts = int64[8] on the device.
+ *       mode 0, multi-class micro-F1 of the argmax (impl/metrics.py:15-20): target int64[n] (ldt ignored); counts =
+ *         {correct, n, 0, 0, 0, ..}, correct = rows whose argmax equals the target.  The argmax is numpy's: the lowest
+ *         index among equal maxima, a NaN beats every number (the first NaN wins).  A target outside [0, K) is never
+ *         correct; it is not an error.
+ *       mode 1, binary / multi-label micro-F1 of (logit > 0) (impl/metrics.py:5-12): target float[n, K], row stride
+ *         ldt; the prediction bit is pred > 0 (NaN and -0.0 give 0); counts = {tp, fp, fn, tn, invalid, ..}, invalid =
+ *         target elements that are neither 0.0 nor 1.0 (they enter none of the four cells).
+ *       K <= GLASS_EVAL_F1_LANE_K: one lane per row (float4 loads when the pointers and strides are 16-byte aligned);
+ *       wider: one wave per row with a cross-lane (value, index) reduction.
+ *     glass_eval_auroc_counts_f32 (impl/metrics.py:23-27): counts = int64[4 * K]; per column k {twoU, P, N, invalid},
+ *       twoU = sum over rows i with label 1 and rows j with label 0 of 2 [s_i > s_j] + [s_i == s_j] (the Mann-Whitney
+ *       pair count, twice: AUROC = twoU / (2 P N)); P / N = labels equal to 1.0 / 0.0; invalid = scores that are not finite
+ *       (scikit-learn refuses NaN and infinities alike) and labels that are neither.  twoU itself takes plain IEEE
+ *       compares on the fp32 values: -0.0 == 0.0, infinities order like numbers, a NaN score adds nothing.
+ *       Grid (ceil(n / 256), K): a lane keeps row i, the workgroup walks every j through LDS tiles — O(n^2 K) compares,
+ *       meant for evaluation splits: glass_eval_auroc_supported(n, K) = 1 while 1 <= n <= GLASS_EVAL_AUROC_MAX_ROWS and
+ *       1 <= K <= 256.
+ *     Checked on the host before any launch: null pointers, n < 1, K < 1, ld < K -> GLASS_E_ARG; K > 256, an unknown
+ *     mode, n over the AUROC limit, n * max(ld) * 4 >= 2^31 -> GLASS_E_UNSUPPORTED (the caller scores on the host). */
+#define GLASS_EVAL_F1_LANE_K 16
+#define GLASS_EVAL_AUROC_MAX_ROWS 65536
+int glass_eval_f1_counts_f32(const float* pred, int64_t ldp, const void* target, int64_t ldt, int64_t n, int64_t K, int mode,
+                             int64_t* counts, void* stream);
+int glass_eval_auroc_supported(int64_t n, int64_t K);
+int glass_eval_auroc_counts_f32(const float* score, int64_t lds, const float* label, int64_t ldl, int64_t n, int64_t K,
+                                int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
