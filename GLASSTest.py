@@ -41,7 +41,12 @@ def parse_args(argv=None):
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--use_seed", action="store_true")
     p.add_argument("--max_epoch", type=int, default=300, help="(extension) cap on epochs per repeat")
-    return p.parse_args(argv)
+    p.add_argument("--clip", type=float, default=None,
+                   help="(extension) clip the gradient's global L2 norm to this value before every Adam update (default: off)")
+    args = p.parse_args(argv)
+    if args.clip is not None and not args.clip > 0:
+        p.error("--clip must be positive")
+    return args
 
 
 def set_seed(seed: int):
@@ -178,6 +183,9 @@ class Run:
             self.split()
             model = self.build_model(hidden_dim, conv_layer, dropout, jk, pool, z_ratio, aggr)
             optimizer = Adam(model.parameters(), lr=lr)  # (impl.train.train runs it as one fused launch inside the step's graph)
+            if self.args.clip is not None:
+                # torch keeps unknown group keys; the step reads this one (norm launch + clipped Adam inside the step's graph)
+                optimizer.param_groups[0]["max_grad_norm"] = self.args.clip
             scheduler = lr_scheduler.ReduceLROnPlateau(optimizer, factor=resi, min_lr=5e-5)
             epochs, seconds, val, tst = self.fit_once(model, optimizer, scheduler, self.loaders(batch_size), horizon, horizon)
             print(f"end: epoch {epochs}, train time {seconds:.2f} s, val {val:.3f}, tst {tst:.3f}", flush=True)

@@ -179,6 +179,9 @@ SIGNATURES = {
                                        c_uint64, c_int, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P]),
     "glass_comb_eff_bwd_gn_src_supported": (c_int, [_I, _I]),
     "glass_adam_step_f32": (c_int, [_P, _P, _P, _P, _I, _P, c_double, c_double, c_double, c_double, _P, _P]),
+    "glass_grad_norm_chunk": (c_int64, []),
+    "glass_grad_norm_f32": (c_int, [_P, _I, _P, _I, c_float, _P, _P]),
+    "glass_adam_step_clip_f32": (c_int, [_P, _P, _P, _P, _I, _P, c_double, c_double, c_double, c_double, _P, _P, _P]),
     "glass_seg_extract_count": (c_int, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, c_int, _P, _P, _P, _P]),
     "glass_seg_extract_fill": (c_int, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "glass_seg_collate": (c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I,

@@ -199,6 +199,36 @@ __device__ __forceinline__ void adam_ticket(int64_t* __restrict__ step_dev, int6
     }
 }
 
+// The stand-alone Adam launch over a flat arena, as a body: glass_adam_step_f32 (linear.hip) is CLIP = false;
+// glass_adam_step_clip_f32 (gradclip.hip) is CLIP = true — the gradient is scaled by coef[0] on load, BEFORE the weight-decay
+// term (clip_grad_norm_ scales the raw gradient, the optimizer adds the decay), and the scaled value is stored back.
+// (__fmul_rn: the product is rounded on its own, never contracted into the moment update — what is stored is what is used.)
+template <bool CLIP, typename G>
+__device__ __forceinline__ void adam_arena_body(float* __restrict__ p, G* __restrict__ g, float* __restrict__ m,
+                                                float* __restrict__ v, int64_t n, const float* __restrict__ lr_dev, float beta1,
+                                                float beta2, float eps, float weight_decay, int64_t* __restrict__ step_dev,
+                                                const float* __restrict__ coef) {
+    const int64_t step_now = step_dev[0] + 1;
+    const AdamCoef c = adam_coef(step_now, lr_dev[0], beta1, beta2, eps, weight_decay);
+    if constexpr (CLIP) {
+        const float s = coef[0];
+        for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBlock) {
+            const float gk = __fmul_rn(g[k], s);
+            g[k] = gk;
+            adam_update(c, p, gk, m, v, k);
+        }
+    } else {
+        for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBlock)
+            adam_update(c, p, g[k], m, v, k);
+    }
+    adam_ticket(step_dev, step_now);
+}
+
+inline unsigned adam_arena_blocks(int64_t n) {
+    const int64_t blocks = ceil_div(n, kBlock);
+    return (unsigned)(blocks > 2048 ? 2048 : blocks);
+}
+
 // ---- LDS-only barrier and buffer addressing (the staged dense kernels) -----------------------------------------------
 // lds_barrier: s_waitcnt lgkmcnt(0) + s_barrier — what a stage hand-over through LDS needs.  __syncthreads() also carries a
 // release fence that waits for vmcnt(0), i.e. it DRAINS the wave's outstanding global loads: a prefetch across it is no

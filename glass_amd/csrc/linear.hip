@@ -555,11 +555,7 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(float* __restrict__ p, con
                                                       const float* __restrict__ lr_dev, float beta1, float beta2,
                                                       float eps, float weight_decay,
                                                       int64_t* __restrict__ step_dev) {
-    const int64_t step_now = step_dev[0] + 1;
-    const AdamCoef c = adam_coef(step_now, lr_dev[0], beta1, beta2, eps, weight_decay);
-    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBlock)
-        adam_update(c, p, g[k], m, v, k);
-    adam_ticket(step_dev, step_now);
+    adam_arena_body<false>(p, g, m, v, n, lr_dev, beta1, beta2, eps, weight_decay, step_dev, nullptr);
 }
 
 }  // namespace glass
@@ -821,9 +817,7 @@ extern "C" int glass_adam_step_f32(float* param, const float* grad, float* exp_a
                                    int64_t* step_dev, void* stream) {
     GLASS_REQUIRE(param && grad && exp_avg && exp_avg_sq && lr_dev && step_dev && n > 0, "adam_step: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    int64_t blocks = ceil_div(n, kBlock);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, param, grad, exp_avg, exp_avg_sq, n,
+    hipLaunchKernelGGL(adam_kernel, dim3(adam_arena_blocks(n)), dim3(kBlock), 0, st, param, grad, exp_avg, exp_avg_sq, n,
                        lr_dev, (float)beta1, (float)beta2, (float)eps, (float)weight_decay, step_dev);
     return launch_status("glass_adam_step_f32");
 }

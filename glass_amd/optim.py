@@ -12,10 +12,30 @@ follows a scheduler):
                 state (`exp_avg`, `exp_avg_sq`) becomes views into the flat moment buffers, `step` is republished once per
                 epoch — `optimizer.state_dict()` / `load_state_dict()` / a later eager `optimizer.step()` all see and
                 continue the same state.  impl.train.train does this for the caller; nothing repo-specific is needed.
+
+Clipping of the gradient's global L2 norm (K9c) is one switch for both front ends: `param_groups[0]["max_grad_norm"]`
+(FlatAdam's `max_grad_norm` keyword, `set_max_grad_norm` on a plain torch optimizer — torch keeps unknown group keys).  With it
+the update is never fused into the step's last launch: the norm needs the whole gradient before any parameter moves.
 """
 import torch
 
 from . import _lib
+
+
+def _checked_max_grad_norm(value):
+    """None (clipping off) or a positive float; anything else is a ValueError."""
+    if value is None:
+        return None
+    v = float(value)
+    if not v > 0.0:  # (zero, negative, NaN)
+        raise ValueError(f"max_grad_norm must be positive or None, got {value!r}")
+    return v
+
+
+def set_max_grad_norm(optimizer, value):
+    """Switch clipping by global norm on (value > 0) or off (None) for `optimizer`: a FlatAdam, or the plain torch.optim.Adam
+    that impl.train.train adopts."""
+    optimizer.param_groups[0]["max_grad_norm"] = _checked_max_grad_norm(value)
 
 
 class _FlatAdamCore:
@@ -31,6 +51,15 @@ class _FlatAdamCore:
         self.step_dev_shard = torch.zeros(2, dtype=torch.int64, device=dev)  # the same for the sharded big bucket
         self.lr_dev = torch.full((1, ), float(lr), dtype=torch.float32, device=dev)
         self._lr_host = float(lr)
+        # clipping (K9c): chunk partials of the norm launch, and (norm, clip coefficient) of the last clipped step — device
+        # memory a captured step writes; reading it needs no sync of the step itself
+        chunk = int(_lib.load().glass_grad_norm_chunk())
+        self._norm_partials = torch.zeros(max(1, -(-arena.flat.numel() // chunk)), dtype=torch.float64, device=dev)
+        self.grad_norm_dev = torch.zeros(2, dtype=torch.float32, device=dev)
+
+    def max_grad_norm(self):
+        """param_groups[0]['max_grad_norm'] validated: None (off) or a positive float."""
+        return _checked_max_grad_norm(self.param_groups[0].get("max_grad_norm"))
 
     def sync_lr(self):
         """Mirror a scheduler's change of param_groups[0]['lr'] into device memory (call outside a
@@ -41,30 +70,44 @@ class _FlatAdamCore:
             self._lr_host = lr
 
     def hyper(self):
-        """(beta1, beta2, eps, weight_decay): the values a captured step has baked in (TrainStep re-captures when they change)."""
+        """(beta1, beta2, eps, weight_decay, max_grad_norm): the values a captured step has baked in (TrainStep re-captures when
+        they change).  max_grad_norm is None while clipping is off."""
         g = self.param_groups[0]
-        return (float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+        return (float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.max_grad_norm())
 
     def fusable(self):
-        """The update can ride in the step program's last launch (glass_embed_norm_bwd_adam_f32): one unsharded arena."""
+        """The update can ride in the step program's last launch (glass_embed_norm_bwd_adam_f32): one unsharded arena, no
+        clipping (the norm needs the whole gradient before any parameter moves: separate launches over the finished arena)."""
+        if self.max_grad_norm() is not None:
+            return False
         return not self.arena.sharded() and self.arena.attached() and getattr(self.arena, "_peer", None) is None
 
     def fused_args(self):
         """(param, grad, exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps, weight_decay, step_dev) of the whole arena."""
         a = self.arena
         return (a.flat_param.data_ptr(), a.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                a.flat_param.numel(), self.lr_dev.data_ptr(), *self.hyper(), self.step_dev.data_ptr())
+                a.flat_param.numel(), self.lr_dev.data_ptr(), *self.hyper()[:4], self.step_dev.data_ptr())
 
     def zero_grad(self, set_to_none=False):
         self.arena.zero()
 
     @torch.no_grad()
     def step(self, closure=None):
-        b1, b2, eps, wd = self.hyper()
-        if not torch.cuda.is_current_stream_capturing():
-            self.sync_lr()
+        b1, b2, eps, wd, clip = self.hyper()
         a = self.arena
         peer = getattr(a, "_peer", None)
+        if clip is not None:  # what clipping does not serve is refused before anything is launched
+            if a.sharded():
+                raise _lib.GlassHipError("max_grad_norm with a sharded gradient arena (the embedding-sized bucket of "
+                                         "dist.GradExchange) is not supported: the global norm would need a cross-rank sum")
+            if peer is not None:
+                raise _lib.GlassHipError("max_grad_norm with an attached one-shot peer exchange (glass_amd/peer.py) is not "
+                                         "supported: its launch updates the parameters while it reduces the gradient")
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_lr()
+        if clip is not None:
+            self._step_clipped(b1, b2, eps, wd, clip)
+            return
         if peer is not None:  # one-shot peer exchange + Adam as ONE launch (glass_amd/peer.py); all_reduce_mean() was a no-op
             peer.step(self)
             return
@@ -90,10 +133,28 @@ class _FlatAdamCore:
         launch(p_sh, ex.shard_grad, m_sh, v_sh, self.step_dev_shard)
         ex.gather_params()
 
+    def _step_clipped(self, b1, b2, eps, wd, clip):
+        """Norm of the whole (all-reduced mean) gradient arena, then Adam on the gradient scaled by the clip coefficient: 3
+        launches.  Only the whole, unsharded arena is served (step() has refused the rest)."""
+        a = self.arena
+        n = a.flat_param.numel()
+        if n == 0:
+            return
+        lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
+        out = self.grad_norm_dev
+        rc = lib.glass_grad_norm_f32(a.flat.data_ptr(), n, self._norm_partials.data_ptr(), self._norm_partials.numel(), clip,
+                                     out.data_ptr(), stream)
+        _lib.check(rc, "glass_grad_norm_f32")
+        rc = lib.glass_adam_step_clip_f32(a.flat_param.data_ptr(), a.flat.data_ptr(), self.exp_avg.data_ptr(),
+                                          self.exp_avg_sq.data_ptr(), n, self.lr_dev.data_ptr(), b1, b2, eps, wd,
+                                          self.step_dev.data_ptr(), out.data_ptr() + out.element_size(), stream)
+        _lib.check(rc, "glass_adam_step_clip_f32")
+
 
 class FlatAdam(_FlatAdamCore, torch.optim.Optimizer):
-    def __init__(self, arena, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        torch.optim.Optimizer.__init__(self, arena.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def __init__(self, arena, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+        torch.optim.Optimizer.__init__(self, arena.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                                                max_grad_norm=_checked_max_grad_norm(max_grad_norm)))
         self._init_device_state(arena, lr)
 
 

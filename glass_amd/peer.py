@@ -87,7 +87,7 @@ class PeerExchange:
 
     def step(self, opt, mean_out=None):
         """The fused exchange + Adam launch for FlatAdam / AdoptedAdam `opt` (whole arena)."""
-        b1, b2, eps, wd = opt.hyper()
+        b1, b2, eps, wd = opt.hyper()[:4]  # (a clipped step never gets here: optim.step raises for clip + peer)
         a = self.arena
         rc = _lib.load().glass_peer_allreduce_adam_f32(ctypes.byref(self._grp), self.n, a.flat_param.data_ptr(), opt.exp_avg.data_ptr(),
                                                        opt.exp_avg_sq.data_ptr(), opt.lr_dev.data_ptr(), b1, b2, eps, wd,

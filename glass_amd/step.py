@@ -54,6 +54,7 @@ class TrainStep:
         # the launch that stores the loss; other forms add one captured kernel) so that an epoch loop needs no per-step launch
         self._loss_sum = torch.zeros((), dtype=torch.float32, device=x.device)
         self._hyper = None              # (betas, eps, weight_decay) baked into the captured optimizer launch
+        self._clip = None               # max_grad_norm baked into the capture (None: no clipping launches in it)
         self._one = torch.ones((), device=x.device)
         self._g_fb = self._g_tail = None
         self._split = False
@@ -68,6 +69,12 @@ class TrainStep:
         self.exchange_enabled = True    # bench.py: False = skip the collectives (timing of the exposed share; ranks diverge)
         self._head_sig = None           # batch shape / target row size baked into a capture whose head launch labels the batch
         self._recapture = False         # the label form (in the head launch / eager in front of the step) changed since the capture
+
+    def _opt_hyper(self):
+        """(hyper, clip) the optimizer would bake into a capture now: optim's hyper() cut into its four Adam values and
+        max_grad_norm (clipping adds launches to the step: a change needs a new capture like any of the others)."""
+        h = self.opt.hyper() if hasattr(self.opt, "hyper") else None
+        return (h, None) if h is None else (tuple(h[:4]), h[4] if len(h) > 4 else None)
 
     # -- the step body, split at the collective ---------------------------------------------------
     def _fused_head(self):
@@ -389,11 +396,12 @@ class TrainStep:
         self._labels.set_epoch(pos_all, y_all, idx_batches, self._pos, self._y, wrap=wrap)
         self._labels.in_head = True
         sig = self._labels.head_signature()
-        hyper = self.opt.hyper() if hasattr(self.opt, "hyper") else None
-        if first or not self.graphed or hyper != self._hyper or sig != self._head_sig or not was_head or self._recapture:
+        hyper, clip = self._opt_hyper()
+        if (first or not self.graphed or (hyper, clip) != (self._hyper, self._clip) or sig != self._head_sig or not was_head or
+                self._recapture):
             if first:
                 self._warmup()   # (eager steps through the same head launch: they consume the first batches of the cursor)
-            self._hyper, self._head_sig, self._recapture = hyper, sig, False
+            self._hyper, self._clip, self._head_sig, self._recapture = hyper, clip, sig, False
             self._capture()
             self._labels.set_epoch(pos_all, y_all, idx_batches, self._pos, self._y, wrap=wrap)  # cursor back to batch 0
         return True
@@ -423,14 +431,14 @@ class TrainStep:
             self._labels.in_head = False
             self._recapture = self.graphed
         self._load_batch(pos, y, index)
-        hyper = self.opt.hyper() if hasattr(self.opt, "hyper") else None
-        if first or (self.graphed and (hyper != self._hyper or self._recapture)):
+        hyper, clip = self._opt_hyper()
+        if first or (self.graphed and ((hyper, clip) != (self._hyper, self._clip) or self._recapture)):
             self._recapture = False
-            # (betas / eps / weight_decay are launch arguments: a changed param_groups entry means a new capture; the learning
-            # rate lives in device memory and needs none)
+            # (betas / eps / weight_decay / max_grad_norm are launch arguments: a changed param_groups entry means a new
+            # capture; the learning rate lives in device memory and needs none)
             if first:
                 self._warmup()
-            self._hyper = hyper
+            self._hyper, self._clip = hyper, clip
             if self.use_graph:
                 self._capture()
         if hasattr(self.opt, "sync_lr"):

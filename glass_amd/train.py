@@ -99,6 +99,9 @@ def train(optimizer, model, dataloader, loss_fn):
     bucket = gdist.bucket_for(model) if gdist.is_distributed() else None
     # (a loss that opts out of fusion — loss_fn._glass_no_fuse — is called as it is, once per step)
     fused_head = hasattr(model, "loss_and_logits") and not getattr(loss_fn, "_glass_no_fuse", False)
+    # param_groups[0]["max_grad_norm"] (glass_amd/optim.py): the flat engine clips inside its own step(); a plain torch optimizer
+    # ignores the key, so this loop honours it with the framework's pass — the switch never silently does nothing
+    clip = None if hasattr(optimizer, "grad_norm_dev") else optimizer.param_groups[0].get("max_grad_norm")
     for batch in dataloader:
         if bucket is None:
             optimizer.zero_grad()
@@ -114,6 +117,8 @@ def train(optimizer, model, dataloader, loss_fn):
         if bucket is not None:
             bucket.all_reduce_mean()
         total_loss.append(loss.detach())
+        if clip is not None:
+            torch.nn.utils.clip_grad_norm_([p for g in optimizer.param_groups for p in g["params"]], clip)
         optimizer.step()
     # one host sync per epoch instead of the reference's .item() per step (train.py:15)
     return _epoch_loss(torch.stack(total_loss).mean(), dataloader)

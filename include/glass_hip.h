@@ -793,6 +793,29 @@ int glass_adam_step_f32(float* param, const float* grad, float* exp_avg, float* 
                         const float* lr_dev, double beta1, double beta2, double eps, double weight_decay,
                         int64_t* step_dev, void* stream);
 
+/* K9c Clipping of the gradient's global L2 norm in front of K9 (torch.nn.utils.clip_grad_norm_ between backward and the
+ *     step of the optimizer built at GLASSTest.py:213), capturable: everything stays in device memory.
+ *     glass_grad_norm_f32: out = float[2]; out[0] = the L2 norm of grad[0..n), out[1] = the clip coefficient
+ *       clamp(max_norm / (out[0] + 1e-6), max = 1), evaluated in fp32 from the fp32-rounded norm (torch's formula; a NaN
+ *       norm gives a NaN coefficient, an infinite one gives 0: nothing is special-cased).  Squares and sums are fp64.
+ *       grad is cut into chunks of glass_grad_norm_chunk() ELEMENTS — a fixed function of n, not of the grid — each summed
+ *       by one workgroup in a fixed order into partials[chunk]; a second one-workgroup launch adds the partials (lane t
+ *       takes partials t, t + 256, .. in index order, then the same fixed tree) and writes out.  No float atomics: the
+ *       result is bitwise repeatable and independent of occupancy.  partials: caller workspace of n_partials >=
+ *       ceil(n / chunk) doubles.  A grad that is not 16-byte aligned takes element loads (same order, same bits).
+ *       GLASS_E_ARG: null pointer, n <= 0, n_partials too small, max_norm negative or NaN, grad / out not 4-byte or
+ *       partials not 8-byte aligned.
+ *     glass_adam_step_clip_f32: glass_adam_step_f32 with every gradient element replaced by g * coef[0] (one fp32
+ *       product, rounded on its own) BEFORE the weight_decay * p term is added; the scaled gradient is stored back into
+ *       grad (what clip_grad_norm_ leaves in p.grad).  coef: device pointer, out + 1 of glass_grad_norm_f32.  Same step
+ *       counter and ticket; with coef[0] == 1 parameters, moments and counter are bitwise those of glass_adam_step_f32. */
+int64_t glass_grad_norm_chunk(void);                                      /* GLASSTest.py:213 */
+int glass_grad_norm_f32(const float* grad, int64_t n, double* partials, int64_t n_partials, float max_norm, float* out,
+                        void* stream);                                    /* GLASSTest.py:213 (+ clip_grad_norm_) */
+int glass_adam_step_clip_f32(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
+                             double beta1, double beta2, double eps, double weight_decay, int64_t* step_dev,
+                             const float* coef, void* stream);            /* GLASSTest.py:213 */
+
 /* ------------------------------------------------------------------------------------------
  * K10  GNN-seg induced subgraphs and their batches (the baseline GNNSeg.py runs beside GLASS)
  *
