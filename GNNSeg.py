@@ -9,7 +9,9 @@ a seeded synthetic graph (glass_amd/synth.py) run with the hyper-parameters and 
 0, the reference's value) grows every subgraph into the radius-K in-ball of its nodes (todatalist(gd, hop)); `--pool
 {ball,centre}` (default ball, the reference's readout over every node of the ball) — centre pools over the subgraph's
 own nodes only, the ones the reference marks in Data.pos, and leaves the rest of the ball as context for the message
-passing; at hop 0 the two are the same run.  GPU only.
+passing; at hop 0 the two are the same run; `--graph_norm {batch,graph}` (default batch, the reference's GraphNorm
+over all rows of a batch) — graph normalises every subgraph over its own rows, so its prediction does not depend on the
+subgraphs batched with it.  GPU only.
 """
 import argparse
 import functools
@@ -49,6 +51,8 @@ def parse_args(argv=None):
     p.add_argument("--hop", type=int, default=0, help="(extension) k_hop_subgraph hops of every subgraph")
     p.add_argument("--pool", type=str, default="ball", choices=("ball", "centre"),
                    help="(extension) readout over the whole ball, or over the subgraph's own nodes")
+    p.add_argument("--graph_norm", type=str, default="batch", choices=("batch", "graph"),
+                   help="(extension) GraphNorm statistics over the whole batch, or over each subgraph's own rows")
     return p.parse_args(argv)
 
 
@@ -124,7 +128,8 @@ class Run:
     def build_model(self, hidden_dim, conv_layer, dropout):
         conv = seg.GConv(self.input_channels, hidden_dim, hidden_dim, conv_layer,
                          conv=seg.MyGINConv if self.mode == "gin" else functools.partial(seg.GCNConv, add_self_loops=False),
-                         activation=nn.ELU(inplace=True), dropout=dropout)
+                         activation=nn.ELU(inplace=True), dropout=dropout,
+                         graph_norm=getattr(getattr(self, "args", None), "graph_norm", "batch"))
         mlp = models.MLP(hidden_dim * conv_layer, hidden_dim, self.output_channels, 2, dropout=dropout,
                          activation=nn.ELU(inplace=True))
         return seg.GNN(conv, mlp, aggr="sum").to(config.device)

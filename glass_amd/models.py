@@ -25,9 +25,10 @@ USE_STACK = os.environ.get("GLASS_STACK", "1") != "0"  # A/B switch: whole-stack
 
 # ---------------------------------------------------------------------------------------------
 class GraphNorm(nn.Module):
-    """Whole-graph GraphNorm (PyG 1.7.2 semantics with batch=None): parameters `weight`, `bias`,
-    `mean_scale` initialised to 1, 0, 1.  `forward` optionally fuses the ELU and the inverted
-    dropout that follow every GraphNorm in the reference (models.py:166,251,258-259)."""
+    """GraphNorm (PyG 1.7.2 semantics): parameters `weight`, `bias`, `mean_scale` initialised to 1, 0, 1.
+    batch=None normalises over all rows as one graph, and `forward` then optionally fuses the ELU and the inverted dropout
+    that follow every GraphNorm in the reference (models.py:166,251,258-259).  With `batch` every graph of a batch is
+    normalised over its own rows (ops.graphnorm_seg); the activation is still fused, dropout is not."""
     def __init__(self, in_channels, eps=1e-5):
         super().__init__()
         self.in_channels, self.eps = in_channels, eps
@@ -40,11 +41,35 @@ class GraphNorm(nn.Module):
         nn.init.zeros_(self.bias)
         nn.init.ones_(self.mean_scale)
 
-    def forward(self, x, batch=None, act=ACT_NONE, p_drop=0.0, call_id=0):
-        if batch is not None:
-            raise NotImplementedError("GLASS only uses whole-graph GraphNorm (batch=None)")
-        return ops.graphnorm(x, self.weight, self.bias, self.mean_scale, self.eps, act, p_drop, call_id,
-                             getattr(self, "_direct_grad", False))
+    def forward(self, x, batch=None, act=ACT_NONE, p_drop=0.0, call_id=0, batch_size=None):
+        """batch: None; or PyG's sorted int64 vector [n] of graph indices — the number of graphs is `batch_size` when given
+        (no device read), else batch[-1] + 1, fetched with the sortedness flag in one read-back; or an ops.SegPtr around the
+        int32 row offsets [B + 1] of the graphs (what seg.SegAdj carries), which costs nothing.  An unsorted batch raises
+        ValueError where it is looked at (without batch_size)."""
+        direct = getattr(self, "_direct_grad", False)
+        if batch is None:
+            return ops.graphnorm(x, self.weight, self.bias, self.mean_scale, self.eps, act, p_drop, call_id, direct)
+        if p_drop > 0:
+            raise ValueError("GraphNorm: dropout is not fused into the per-graph form (batch given); apply it separately")
+        if not isinstance(batch, ops.SegPtr):
+            batch = ops.SegPtr(_seg_ptr_of(batch, x.shape[0], batch_size))
+        return ops.graphnorm_seg(x, batch, self.weight, self.bias, self.mean_scale, self.eps, act, direct)
+
+
+def _seg_ptr_of(batch, n_rows, batch_size=None):
+    """int32 row offsets [B + 1] of a sorted PyG batch vector (int64 [n], graph index per row)."""
+    if not isinstance(batch, torch.Tensor) or batch.dtype != torch.int64 or batch.dim() != 1 or batch.shape[0] != n_rows:
+        raise ValueError(f"GraphNorm: batch must be an int64 vector with one graph index per row of x ({n_rows})")
+    if batch_size is None:
+        if n_rows == 0:
+            batch_size = 0
+        else:
+            last, unsorted, first = torch.stack((batch[-1], (batch[1:] < batch[:-1]).any().to(torch.int64), batch[0])).tolist()
+            if unsorted or first < 0:
+                raise ValueError("GraphNorm: batch must be sorted (non-decreasing graph indices starting at >= 0)")
+            batch_size = last + 1
+    bounds = torch.arange(int(batch_size) + 1, dtype=torch.int64, device=batch.device)
+    return torch.searchsorted(batch, bounds).to(torch.int32)
 
 
 def _act_code(activation):

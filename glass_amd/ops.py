@@ -565,6 +565,78 @@ def graphnorm(x, gamma, beta, alpha, eps=1e-5, act=ACT_NONE, p_drop=0.0, call_id
 
 
 # ---------------------------------------------------------------------------------------------
+# K6s  per-graph GraphNorm over a batch of graphs
+# ---------------------------------------------------------------------------------------------
+class SegPtr:
+    """Marks an int32 device vector [B + 1] as segment POINTERS (row s of the batch's graphs: seg_ptr[s] .. seg_ptr[s + 1] - 1,
+    seg_ptr[0] = 0, seg_ptr[B] = n) — so that it cannot be taken for a PyG batch vector (one graph index per row)."""
+    def __init__(self, seg_ptr):
+        if not isinstance(seg_ptr, torch.Tensor) or seg_ptr.dtype != torch.int32 or seg_ptr.dim() != 1 or seg_ptr.numel() < 1:
+            raise ValueError("SegPtr takes an int32 vector [B + 1]")
+        self.ptr = seg_ptr.contiguous()
+
+    def __len__(self):
+        return self.ptr.numel() - 1
+
+
+class GraphNormSegFn(torch.autograd.Function):
+    """y = act(GraphNorm(x, batch)): mean and variance over each graph's own rows (PyG GraphNorm with a batch vector)."""
+    @staticmethod
+    def forward(ctx, x, seg_ptr, gamma, beta, alpha, eps, act, direct=False):
+        _need_gpu(x, seg_ptr, gamma)
+        x, ldx = _rows(x)
+        n, C = x.shape
+        B = seg_ptr.numel() - 1
+        y = torch.empty((n, C), dtype=torch.float32, device=x.device)
+        stats = torch.empty((2, max(B, 1), C), dtype=torch.float32, device=x.device)
+        g, b, a = gamma.contiguous(), beta.contiguous(), alpha.contiguous()
+        rc = _lib.load().glass_graphnorm_seg_fwd_f32(x.data_ptr(), ldx, y.data_ptr(), C, seg_ptr.data_ptr(), B, C, g.data_ptr(),
+                                                     b.data_ptr(), a.data_ptr(), eps, stats[0].data_ptr(), stats[1].data_ptr(),
+                                                     act, _stream())
+        _lib.check(rc, "glass_graphnorm_seg_fwd_f32")
+        ctx.save_for_backward(x, seg_ptr, g, b, a, stats)
+        ctx.act = act
+        # direct: parameter gradients are accumulated straight into the flat gradient arena
+        ctx.direct = (gamma, beta, alpha) if (direct and all(t.grad is not None for t in (gamma, beta, alpha))) else None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, seg_ptr, g, b, a, stats = ctx.saved_tensors
+        n, C = x.shape
+        B = seg_ptr.numel() - 1
+        dy, lddy = _rows(dy)
+        dx = torch.empty((n, C), dtype=torch.float32, device=x.device)
+        if ctx.direct is not None:
+            dg, db, da = (t.grad for t in ctx.direct)
+            accumulate = 1
+        else:
+            dparams = torch.empty((3, C), dtype=torch.float32, device=x.device)
+            dg, db, da = dparams[0], dparams[1], dparams[2]
+            accumulate = 0
+        lib = _lib.load()
+        from . import graph as ggraph
+        ws = _scratch(("graphnorm_seg", C, ggraph._ws_branch), x.device, lib.glass_graphnorm_seg_ws_bytes(B, C))
+        rc = lib.glass_graphnorm_seg_bwd_f32(dy.data_ptr(), lddy, x.data_ptr(), x.stride(0) if n > 1 else max(C, x.stride(0)),
+                                             dx.data_ptr(), C, seg_ptr.data_ptr(), B, C, g.data_ptr(), b.data_ptr(), a.data_ptr(),
+                                             stats[0].data_ptr(), stats[1].data_ptr(), dg.data_ptr(), db.data_ptr(), da.data_ptr(),
+                                             accumulate, ctx.act, ws.data_ptr(), _stream())
+        _lib.check(rc, "glass_graphnorm_seg_bwd_f32")
+        if ctx.direct is not None:
+            return dx, None, None, None, None, None, None, None
+        return dx, None, dg, db, da, None, None, None
+
+
+def graphnorm_seg(x, seg_ptr, gamma, beta, alpha, eps=1e-5, act=ACT_NONE, direct=False):
+    """Per-graph GraphNorm; seg_ptr: int32 [B + 1] device vector of row offsets (a SegPtr or the bare tensor)."""
+    if isinstance(seg_ptr, SegPtr):
+        seg_ptr = seg_ptr.ptr
+    if seg_ptr.dtype != torch.int32 or seg_ptr.dim() != 1 or seg_ptr.numel() < 1:
+        raise GlassHipError(f"graphnorm_seg: seg_ptr must be an int32 vector [B + 1], got {tuple(seg_ptr.shape)} {seg_ptr.dtype}")
+    return GraphNormSegFn.apply(x, seg_ptr.contiguous(), gamma, beta, alpha, float(eps), int(act), bool(direct))
+
+
+# ---------------------------------------------------------------------------------------------
 # K7  subgraph pooling
 # ---------------------------------------------------------------------------------------------
 # Largest padded node matrices (B * Smax entries) the ORDERED, atomic-free scatters stage in LDS (pool.hip kPoolOrderedMax,

@@ -71,9 +71,10 @@ def _ptr(t):
 
 class SegAdj:
     """The normalised adjacency of one batch: fwd = target-major CSR (y[dst] = sum val * x[src]), bwd = its transpose.
-    Takes the place of edge_index in the model calls (ops.spmm reads .fwd / .bwd)."""
-    def __init__(self, fwd, bwd, mode):
-        self.fwd, self.bwd, self.mode = fwd, bwd, mode
+    Takes the place of edge_index in the model calls (ops.spmm reads .fwd / .bwd).  seg_ptr: the int32 device vector
+    [B + 1] of the row offsets of the batch's graphs (what the per-graph GraphNorm of GConv(graph_norm="graph") reads)."""
+    def __init__(self, fwd, bwd, mode, seg_ptr=None):
+        self.fwd, self.bwd, self.mode, self.seg_ptr = fwd, bwd, mode, seg_ptr
         self.n_node = fwd.n_rows
 
     def edge_index(self):
@@ -134,7 +135,8 @@ class SegBatch:
             self._mark = None
             _lib.check(_lib.load().glass_seg_collate(*split, *batch, _stream()), "glass_seg_collate")
         self.adj = SegAdj(CSROperand(brow_in_d, col_in, val_in, n, n, rowptr_host=brow_in.astype(np.int32)),
-                          CSROperand(brow_out_d, col_out, val_out, n, n, rowptr_host=brow_out.astype(np.int32)), ds.mode)
+                          CSROperand(brow_out_d, col_out, val_out, n, n, rowptr_host=brow_out.astype(np.int32)), ds.mode,
+                          seg_ptr=node_off_d)
         self.x = ds.x[self.node_map.to(torch.int64)]
         self.y = ds.y[self.ids]
 
@@ -388,12 +390,18 @@ class MyGINConv(nn.Module):
 
 
 class GConv(nn.Module):
-    """num_layers convolutions in -> hidden -> ... -> out with a whole-batch GraphNorm, the activation and dropout between
-    them; returns the concatenation of every layer's output (GNNSeg.py:70-124).  With an in-place activation (the driver's
-    ELU(inplace=True)) the stored inner outputs are the ACTIVATED tensors, as in the reference."""
+    """num_layers convolutions in -> hidden -> ... -> out with a GraphNorm, the activation and dropout between them; returns
+    the concatenation of every layer's output (GNNSeg.py:70-124).  With an in-place activation (the driver's
+    ELU(inplace=True)) the stored inner outputs are the ACTIVATED tensors, as in the reference.
+    graph_norm: "batch" (the reference: statistics over all rows of the batch, so a subgraph's output depends on the
+    subgraphs batched with it) or "graph" (statistics over each subgraph's own rows, the batch's SegAdj.seg_ptr: a
+    subgraph's output no longer depends on its batch)."""
     def __init__(self, input_channels, hidden_channels, output_channels, num_layers, dropout=0,
-                 activation=nn.ReLU(inplace=True), conv=GCNConv, **kwargs):
+                 activation=nn.ReLU(inplace=True), conv=GCNConv, graph_norm="batch", **kwargs):
         super().__init__()
+        if graph_norm not in ("batch", "graph"):
+            raise ValueError(f"GConv graph_norm {graph_norm!r}: \"batch\" or \"graph\"")
+        self.graph_norm = graph_norm
         dims = [input_channels] + [hidden_channels] * (num_layers - 1) + [output_channels]
         self.convs = nn.ModuleList([conv(in_channels=dims[i], out_channels=dims[i + 1], **kwargs)
                                     for i in range(num_layers)])
@@ -411,14 +419,19 @@ class GConv(nn.Module):
     def forward(self, x, edge_index, edge_weight, z=None):
         code = _act_code(self.activation)
         inplace = bool(getattr(self.activation, "inplace", False))
+        batch = None
+        if self.graph_norm == "graph":
+            if getattr(edge_index, "seg_ptr", None) is None:
+                raise TypeError("GConv(graph_norm=\"graph\") needs the SegAdj of a collated batch (its seg_ptr)")
+            batch = ops.SegPtr(edge_index.seg_ptr)
         xs = []
         for layer, conv in enumerate(self.convs[:-1]):
             h = conv(x, edge_index, edge_weight)
             if inplace and code is not None:
-                h = self.gns[layer](h, act=code)  # GraphNorm + activation in one kernel: the tensor the reference stores
+                h = self.gns[layer](h, batch, act=code)  # GraphNorm + activation in one kernel: the tensor the reference stores
                 xs.append(h)
             else:
-                pre = self.gns[layer](h)
+                pre = self.gns[layer](h, batch)
                 h = self.activation(pre.clone() if inplace else pre)
                 xs.append(h if inplace else pre)
             x = F.dropout(h, p=self.dropout, training=self.training)

@@ -209,6 +209,30 @@ int glass_graphnorm_bwd_from_stats_f32(const float* dy, int64_t lddy, const floa
                                        const double* partial, int64_t nblk, float* dgamma, float* dbeta,
                                        float* dalpha, int accumulate, int act, float p_drop, const uint64_t* rng_state,
                                        uint64_t call_id, void* ws, void* stream);
+/* K6s Per-graph GraphNorm over a batch of graphs (PyG GraphNorm.forward(x, batch): statistics over each graph's own rows).
+ *     Segment s = rows seg_ptr[s] .. seg_ptr[s + 1] - 1; seg_ptr = int32[B + 1] in device memory, non-decreasing, seg_ptr[0] = 0
+ *     (the node offsets glass_seg_collate takes).  Per segment and column, two-pass in fp64:
+ *       mu = mean_rows(x) (row count clamped to >= 1); o = x - alpha*mu; y = act(gamma * o * rsqrt(mean_rows(o^2) + eps) + beta)
+ *     mu, rstd = float[B * C], saved for the backward.  An empty segment writes no row (mu = 0, rstd = rsqrt(eps)).
+ *     One workgroup per segment; how a segment is summed depends on its row count and C alone, so the same rows give the
+ *     same bits whatever the batch around them.  A segment of at most glass_graphnorm_seg_lds_rows(C) rows is staged in LDS
+ *     (its operands are read once); a larger one re-reads global memory, with the same arithmetic.  C <= 512; 16-byte vector
+ *     accesses where C % 4 == 0, every ld % 4 == 0 and the matrices are 16-byte aligned, element accesses in the same
+ *     summation order otherwise.  Row offsets are 64-bit.
+ *     backward: dx, and dgamma / dbeta / dalpha (NULL = not wanted; accumulate != 0 adds into them) summed over ALL segments:
+ *     every segment writes three fp64 column sums to ws (glass_graphnorm_seg_ws_bytes(B, C), 8-byte aligned) and a second
+ *     launch folds them in an order that depends on B alone — no float atomic, bitwise repeatable.  beta is read to
+ *     recompute the pre-activation values (may be NULL with GLASS_ACT_NONE).  Enqueue only; capturable. */
+int64_t glass_graphnorm_seg_lds_rows(int64_t C);                          /* GNNSeg.py:103-104,118; impl/models.py:51,60 */
+int64_t glass_graphnorm_seg_ws_bytes(int64_t B, int64_t C);               /* GNNSeg.py:103-104,118; impl/models.py:51,60 */
+int glass_graphnorm_seg_fwd_f32(const float* x, int64_t ldx, float* y, int64_t ldy, const int32_t* seg_ptr, int64_t B,
+                                int64_t C, const float* gamma, const float* beta, const float* alpha, float eps, float* mu,
+                                float* rstd, int act, void* stream);      /* GNNSeg.py:103-104,118; impl/models.py:51,60 */
+int glass_graphnorm_seg_bwd_f32(const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dx, int64_t lddx,
+                                const int32_t* seg_ptr, int64_t B, int64_t C, const float* gamma, const float* beta,
+                                const float* alpha, const float* mu, const float* rstd, float* dgamma, float* dbeta,
+                                float* dalpha, int accumulate, int act, void* ws,
+                                void* stream);                            /* GNNSeg.py:103-104,118; impl/models.py:51,60 */
 int glass_rng_advance(uint64_t* rng_state, void* stream); /* rng_state[1] += 1 */
 /*     Measurement aid (bench.py `step_floor`): launch a kernel that does nothing with the given grid / block / dynamic-LDS
  *     geometry — the training step's chain of launches replayed with these is the latency floor of that chain. */
