@@ -43,6 +43,9 @@ def parse_args(argv=None):
     p.add_argument("--max_epoch", type=int, default=300, help="(extension) cap on epochs per repeat")
     p.add_argument("--clip", type=float, default=None,
                    help="(extension) clip the gradient's global L2 norm to this value before every Adam update (default: off)")
+    p.add_argument("--class_weight", type=str, default="none", choices=("none", "balanced"),
+                   help="(extension) balanced: class weights (multi-class) / pos_weight (binary, multi-label) from the training "
+                        "split's label counts, applied inside the fused loss (default: none)")
     args = p.parse_args(argv)
     if args.clip is not None and not args.clip > 0:
         p.error("--clip must be positive")
@@ -94,6 +97,10 @@ class Run:
         self.trn = SubGDataset.GDataset(*g.get_split("train"))
         self.val = SubGDataset.GDataset(*g.get_split("valid"))
         self.tst = SubGDataset.GDataset(*g.get_split("test"))
+        if getattr(a, "class_weight", "none") == "balanced":
+            # weights from the TRAINING split only; the marker classes carry them into the captured step (losses.fusable_spec)
+            from glass_amd import losses
+            self.loss_fn = losses.balanced_loss(self.trn.y, self.output_channels).to(config.device)
 
     def loaders(self, batch_size):
         """(train, valid, test) loaders.  With --use_maxzeroone every batch is labeled by utils.MaxZOZ and the training

@@ -53,6 +53,9 @@ def parse_args(argv=None):
                    help="(extension) readout over the whole ball, or over the subgraph's own nodes")
     p.add_argument("--graph_norm", type=str, default="batch", choices=("batch", "graph"),
                    help="(extension) GraphNorm statistics over the whole batch, or over each subgraph's own rows")
+    p.add_argument("--class_weight", type=str, default="none", choices=("none", "balanced"),
+                   help="(extension) balanced: class weights (multi-class) / pos_weight (binary, multi-label) from the training "
+                        "split's label counts, applied inside the fused head + loss (default: none)")
     return p.parse_args(argv)
 
 
@@ -119,6 +122,10 @@ class Run:
         self.trn, self.val, self.tst = (seg.GsDataset(*g.get_split(s), mode=self.mode, base=base, hop=self.args.hop,
                                                       pool=self.args.pool)
                                         for s in ("train", "valid", "test"))
+        if getattr(self.args, "class_weight", "none") == "balanced":
+            # weights from the TRAINING split only; the marker classes carry them into the fused head (losses.fusable_spec)
+            from glass_amd import losses
+            self.loss_fn = losses.balanced_loss(g.get_split("train")[-1], self.output_channels).to(config.device)
 
     def loaders(self, batch_size):
         return (seg.GsDataloader(self.trn, batch_size, shuffle=True, drop_last=True),

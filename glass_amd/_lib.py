@@ -167,6 +167,19 @@ SIGNATURES = {
     "glass_head_mlp_loss_bwd_f32": (c_int, [_P, _I, _P, _P, _P, _P, _P, c_int, c_int, c_float, _P, c_uint64, _P, _I, _I, _I,
                                             _I, _P, _P, _I, _P, _P, _P, _P, c_int, _P]),
     "glass_head_mlp_f32": (c_int, [_P, _I, _P, _P, _P, _P, c_int, _I, _I, _I, _I, _P, _I, _P]),
+    # the weighted siblings: (class_weight, pos_weight) just before stream
+    "glass_head_loss_fwd_w_f32": (c_int, [_P, _I, _P, _P, _P, c_int, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "glass_head_loss_bwd_w_f32": (c_int, [_P, _I, _P, _P, _P, c_int, _P, _I, _I, _I, _P, _I, _P, _P, c_int, _P, _P, _P]),
+    "glass_head_mlp_loss_fwd_w_f32": (c_int, [_P, _I, _P, _P, _P, _P, _P, c_int, c_int, c_float, _P, c_uint64, _I, _I, _I, _I,
+                                              _P, _P, _P, _P, _P, _P, _P]),
+    "glass_head_mlp_loss_bwd_w_f32": (c_int, [_P, _I, _P, _P, _P, _P, _P, c_int, c_int, c_float, _P, c_uint64, _P, _I, _I, _I,
+                                              _I, _P, _P, _I, _P, _P, _P, _P, c_int, _P, _P, _P]),
+    "glass_readout_train_w_f32": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, c_int, _P, _P, _P, c_int, _I, _P, _P, _P, _P, _P, _I,
+                                          _P, _P, c_int, _P, _P, _P, c_int, _P, _I, _I, _P, _P, _P, _P, _P, c_int, _P, _P, _P,
+                                          _P, _P]),
+    "glass_readout_max_train_w_f32": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, c_int, _I, _P, _P, _P, _P, _P, _I,
+                                              _P, _P, c_int, _P, _P, _P, c_int, _P, _I, _I, _P, _P, _P, _P, _P, c_int, _P, _P, _P,
+                                              _P, _P]),
     "glass_batch_labels_ws_bytes": (c_int64, [_I]),
     "glass_batch_labels": (c_int, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, c_int, _P]),
     "glass_batch_labels_gather": (c_int, [_P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, c_int, _P]),

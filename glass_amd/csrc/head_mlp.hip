@@ -47,7 +47,8 @@ __device__ __forceinline__ float mlp_act_grad(int act, float h) {
 // TRAIN: lane 0 of wave 0 finishes the K-term softmax / sigmoid and the row's loss term exactly as head_logits_kernel
 // does; (head_loss.h: head_loss_row); the mean is head_mlp_loss_mean_kernel's.  Evaluation (TRAIN = false): the logits are all that is written — same
 // sums in the same order, so they are bitwise the training entry's at p = 0.
-template <bool TRAIN>
+// WT: the weighted losses (head_loss.h; cw / pw nullable) — launched only when one of them is set.
+template <bool TRAIN, bool WT>
 __global__ __launch_bounds__(kBlock) void head_mlp_fwd_kernel(const float* __restrict__ pooled, int64_t ldp,
                                                               const float* __restrict__ W1, const float* __restrict__ b1,
                                                               const float* __restrict__ W2, const float* __restrict__ b2,
@@ -55,7 +56,8 @@ __global__ __launch_bounds__(kBlock) void head_mlp_fwd_kernel(const float* __res
                                                               const uint64_t* __restrict__ rng, int C, int Hd, int K,
                                                               int stage, float* __restrict__ hidden_pre,
                                                               float* __restrict__ logits, int64_t ldl,
-                                                              float* __restrict__ prob, float* __restrict__ loss_rows) {
+                                                              float* __restrict__ prob, float* __restrict__ loss_rows,
+                                                              const float* __restrict__ cw, const float* __restrict__ pw) {
     extern __shared__ float lds[];  // hidden row [Hd], then the pooled row [C] when staged
     __shared__ float zs[kMaxK];
     float* hs = lds;
@@ -90,7 +92,10 @@ __global__ __launch_bounds__(kBlock) void head_mlp_fwd_kernel(const float* __res
         return;
     }
     if (tid != 0) return;
-    loss_rows[b] = head_loss_row(zs, target, mode, b, K, logits, ldl, prob);
+    if constexpr (WT)
+        loss_rows[b] = head_loss_row(zs, target, mode, b, K, logits, ldl, prob, cw, pw);
+    else
+        loss_rows[b] = head_loss_row(zs, target, mode, b, K, logits, ldl, prob);
 }
 
 // mean of the B row terms, summed in index order (as head.hip's)
@@ -99,9 +104,18 @@ __global__ __launch_bounds__(kBlock) void head_mlp_loss_mean_kernel(const float*
     head_loss_mean(loss_rows, B, denom, loss);
 }
 
+// weighted cross-entropy: divided by the batch's weight sum, recomputed from target and cw
+__global__ __launch_bounds__(kBlock) void head_mlp_loss_mean_w_kernel(const float* __restrict__ loss_rows, int B, float denom,
+                                                                      float* __restrict__ loss, const float* __restrict__ cw,
+                                                                      const void* __restrict__ target, int K) {
+    head_loss_mean(loss_rows, B, denom, loss, cw, target, K);
+}
+
 // Backward, launch 1 — one workgroup per subgraph b: dlogits[b, :] staged in LDS, then per hidden unit j (thread-strided)
 // da = sum_k dlogits[k] W2[k, j], dh = da * act'(h * keep) * keep with the regenerated mask; dh[b, :] and a[b, :] =
 // act(h * keep) go to the workspace (launch 2 sums them over b) and dh stays in LDS for dpooled[b, :] = dh @ W1.
+// WT (both backward kernels): dlogits of the weighted losses; with class weights each workgroup recomputes the weight sum.
+template <bool WT>
 __global__ __launch_bounds__(kBlock) void head_mlp_bwd_rows_kernel(const float* __restrict__ W1, const float* __restrict__ W2,
                                                                    const float* __restrict__ hidden_pre,
                                                                    const float* __restrict__ prob,
@@ -109,16 +123,23 @@ __global__ __launch_bounds__(kBlock) void head_mlp_bwd_rows_kernel(const float* 
                                                                    Drop drop, const uint64_t* __restrict__ rng,
                                                                    const float* __restrict__ gl, int B, int C, int Hd, int K,
                                                                    float* __restrict__ dh_ws, float* __restrict__ a_ws,
-                                                                   float* __restrict__ dpooled, int64_t lddp) {
+                                                                   float* __restrict__ dpooled, int64_t lddp,
+                                                                   const float* __restrict__ cw, const float* __restrict__ pw) {
     __shared__ float dl[kMaxK];
     __shared__ float dhs[kMlpMaxHd];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float scale = gl[0] / head_loss_denom(mode, B, K);
+    float scale;
+    if constexpr (WT) {
+        __shared__ double wred[kBlock];
+        scale = head_loss_scale(gl, mode, B, K, cw, target, wred);
+    } else {
+        scale = gl[0] / head_loss_denom(mode, B, K);
+    }
     if (drop.p > 0.f) {
         drop.seed = rng[0];
         drop.step = rng[1];
     }
-    for (int k = tid; k < K; k += kBlock) dl[k] = dlogit(prob, target, mode, b, k, K, scale);
+    for (int k = tid; k < K; k += kBlock) dl[k] = WT ? dlogit(prob, target, mode, b, k, K, scale, cw, pw) : dlogit(prob, target, mode, b, k, K, scale);
     __syncthreads();
     for (int j = tid; j < Hd; j += kBlock) {
         float da = 0.f;
@@ -143,6 +164,7 @@ __global__ __launch_bounds__(kBlock) void head_mlp_bwd_rows_kernel(const float* 
 // Backward, launch 2 — one workgroup per weight row.  Workgroups 0..K-1: dW2[k, :] (+)= sum_b dlogits[b, k] a[b, :],
 // db2[k] (+)= sum_b dlogits[b, k].  Workgroups K..K+Hd-1: dW1[j, :] (+)= sum_b dh[b, j] pooled[b, :], db1[j] (+)= sum_b
 // dh[b, j].  The row's B coefficients are staged in LDS a tile of kMlpTile at a time; every sum runs over b in index order.
+template <bool WT>
 __global__ __launch_bounds__(kBlock) void head_mlp_bwd_weights_kernel(const float* __restrict__ pooled, int64_t ldp,
                                                                       const float* __restrict__ prob,
                                                                       const void* __restrict__ target, int mode,
@@ -150,12 +172,19 @@ __global__ __launch_bounds__(kBlock) void head_mlp_bwd_weights_kernel(const floa
                                                                       const float* __restrict__ dh_ws,
                                                                       const float* __restrict__ a_ws, float* __restrict__ dW1,
                                                                       float* __restrict__ db1, float* __restrict__ dW2,
-                                                                      float* __restrict__ db2, int accumulate) {
+                                                                      float* __restrict__ db2, int accumulate,
+                                                                      const float* __restrict__ cw, const float* __restrict__ pw) {
     __shared__ float g[kMlpTile];
     const int blk = blockIdx.x, tid = threadIdx.x;
     const bool second = blk < K;            // a row of the second Linear (else of the first)
     const int r = second ? blk : blk - K;   // k or j
-    const float scale = gl[0] / head_loss_denom(mode, B, K);
+    float scale;
+    if constexpr (WT) {
+        __shared__ double wred[kBlock];
+        scale = head_loss_scale(gl, mode, B, K, cw, target, wred);
+    } else {
+        scale = gl[0] / head_loss_denom(mode, B, K);
+    }
     const float* X = second ? a_ws : pooled;
     const int64_t ldx = second ? (int64_t)Hd : ldp;
     const int n = second ? Hd : C;
@@ -170,7 +199,9 @@ __global__ __launch_bounds__(kBlock) void head_mlp_bwd_weights_kernel(const floa
             if (c0 == 0 || B > kMlpTile) {  // (one tile: staged once for every column chunk)
                 __syncthreads();
                 for (int i = tid; i < nb; i += kBlock)
-                    g[i] = second ? dlogit(prob, target, mode, b0 + i, r, K, scale) : dh_ws[(int64_t)(b0 + i) * Hd + r];
+                    g[i] = !second ? dh_ws[(int64_t)(b0 + i) * Hd + r]
+                           : WT    ? dlogit(prob, target, mode, b0 + i, r, K, scale, cw, pw)
+                                   : dlogit(prob, target, mode, b0 + i, r, K, scale);
                 __syncthreads();
             }
             if (c < n) {
@@ -223,25 +254,82 @@ static size_t mlp_fwd_lds(int64_t C, int64_t Hd, int* stage) {
 
 using namespace glass;
 
+static int mlp_weights_check(const char* who, int mode, const float* cw, const float* pw) {
+    if (loss_weights_ok(mode, cw, pw)) return 0;
+    set_error("%s: class_weight goes with cross-entropy, pos_weight with BCE, at most one of them", who);
+    return GLASS_E_UNSUPPORTED;
+}
+
+extern "C" int glass_head_mlp_loss_fwd_w_f32(const float* pooled, int64_t ldp, const float* W1, const float* b1, const float* W2,
+                                             const float* b2, const void* target, int mode, int act, float p_drop,
+                                             const uint64_t* rng_state, uint64_t call_id, int64_t B, int64_t C, int64_t Hd,
+                                             int64_t K, float* hidden_pre, float* logits, float* prob, float* loss,
+                                             const float* class_weight, const float* pos_weight, void* stream) {
+    GLASS_REQUIRE(pooled && W1 && b1 && W2 && b2 && target && hidden_pre && logits && prob && loss,
+                  "head_mlp_loss_fwd: null pointer");
+    GLASS_REQUIRE(mlp_drop_ok(p_drop, rng_state), "head_mlp_loss_fwd: dropout needs 0 <= p < 1 and the rng words");
+    if (int rc = mlp_check("head_mlp_loss_fwd", mode, act, B, C, Hd, K, ldp)) return rc;
+    if (int rc = mlp_weights_check("head_mlp_loss_fwd", mode, class_weight, pos_weight)) return rc;
+    float* loss_rows = prob + B * K;  // prob holds B*K + B floats (as glass_head_loss_fwd_f32's)
+    int stage;
+    const size_t lds = mlp_fwd_lds(C, Hd, &stage);
+    hipStream_t st = (hipStream_t)stream;
+    if (class_weight || pos_weight) {
+        hipLaunchKernelGGL((head_mlp_fwd_kernel<true, true>), dim3((unsigned)B), dim3(kBlock), lds, st, pooled, ldp, W1, b1, W2, b2,
+                           target, mode, act, make_drop(p_drop, call_id, Hd), rng_state, (int)C, (int)Hd, (int)K, stage, hidden_pre,
+                           logits, K, prob, loss_rows, class_weight, pos_weight);
+        hipLaunchKernelGGL(head_mlp_loss_mean_w_kernel, dim3(1), dim3(kBlock), 0, st, loss_rows, (int)B,
+                           head_loss_denom(mode, B, K), loss, class_weight, target, (int)K);
+        return launch_status("glass_head_mlp_loss_fwd_w_f32");
+    }
+    hipLaunchKernelGGL((head_mlp_fwd_kernel<true, false>), dim3((unsigned)B), dim3(kBlock), lds, st, pooled, ldp, W1, b1, W2, b2, target,
+                       mode, act, make_drop(p_drop, call_id, Hd), rng_state, (int)C, (int)Hd, (int)K, stage, hidden_pre, logits, K,
+                       prob, loss_rows, (const float*)nullptr, (const float*)nullptr);
+    hipLaunchKernelGGL(head_mlp_loss_mean_kernel, dim3(1), dim3(kBlock), 0, st, loss_rows, (int)B,
+                       head_loss_denom(mode, B, K), loss);
+    return launch_status("glass_head_mlp_loss_fwd_f32");
+}
+
 extern "C" int glass_head_mlp_loss_fwd_f32(const float* pooled, int64_t ldp, const float* W1, const float* b1, const float* W2,
                                            const float* b2, const void* target, int mode, int act, float p_drop,
                                            const uint64_t* rng_state, uint64_t call_id, int64_t B, int64_t C, int64_t Hd,
                                            int64_t K, float* hidden_pre, float* logits, float* prob, float* loss,
                                            void* stream) {
-    GLASS_REQUIRE(pooled && W1 && b1 && W2 && b2 && target && hidden_pre && logits && prob && loss,
-                  "head_mlp_loss_fwd: null pointer");
-    GLASS_REQUIRE(mlp_drop_ok(p_drop, rng_state), "head_mlp_loss_fwd: dropout needs 0 <= p < 1 and the rng words");
-    if (int rc = mlp_check("head_mlp_loss_fwd", mode, act, B, C, Hd, K, ldp)) return rc;
-    float* loss_rows = prob + B * K;  // prob holds B*K + B floats (as glass_head_loss_fwd_f32's)
-    int stage;
-    const size_t lds = mlp_fwd_lds(C, Hd, &stage);
+    return glass_head_mlp_loss_fwd_w_f32(pooled, ldp, W1, b1, W2, b2, target, mode, act, p_drop, rng_state, call_id, B, C, Hd, K,
+                                         hidden_pre, logits, prob, loss, nullptr, nullptr, stream);
+}
+
+extern "C" int glass_head_mlp_loss_bwd_w_f32(const float* pooled, int64_t ldp, const float* W1, const float* W2,
+                                             const float* hidden_pre, const float* prob, const void* target, int mode, int act,
+                                             float p_drop, const uint64_t* rng_state, uint64_t call_id, const float* grad_loss,
+                                             int64_t B, int64_t C, int64_t Hd, int64_t K, float* ws, float* dpooled, int64_t lddp,
+                                             float* dW1, float* db1, float* dW2, float* db2, int accumulate,
+                                             const float* class_weight, const float* pos_weight, void* stream) {
+    GLASS_REQUIRE(pooled && W1 && W2 && hidden_pre && prob && target && grad_loss && ws && dpooled && dW1 && db1 && dW2 && db2,
+                  "head_mlp_loss_bwd: null pointer");
+    GLASS_REQUIRE(mlp_drop_ok(p_drop, rng_state), "head_mlp_loss_bwd: dropout needs 0 <= p < 1 and the rng words");
+    if (int rc = mlp_check("head_mlp_loss_bwd", mode, act, B, C, Hd, K, ldp)) return rc;
+    if (int rc = mlp_weights_check("head_mlp_loss_bwd", mode, class_weight, pos_weight)) return rc;
+    GLASS_REQUIRE(lddp >= C, "head_mlp_loss_bwd: lddp < C");
+    float* dh_ws = ws;            // [B, Hd]
+    float* a_ws = ws + B * Hd;    // [B, Hd]
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(head_mlp_fwd_kernel<true>, dim3((unsigned)B), dim3(kBlock), lds, st, pooled, ldp, W1, b1, W2, b2, target,
-                       mode, act, make_drop(p_drop, call_id, Hd), rng_state, (int)C, (int)Hd, (int)K, stage, hidden_pre, logits, K,
-                       prob, loss_rows);
-    hipLaunchKernelGGL(head_mlp_loss_mean_kernel, dim3(1), dim3(kBlock), 0, st, loss_rows, (int)B,
-                       head_loss_denom(mode, B, K), loss);
-    return launch_status("glass_head_mlp_loss_fwd_f32");
+    if (class_weight || pos_weight) {
+        hipLaunchKernelGGL(head_mlp_bwd_rows_kernel<true>, dim3((unsigned)B), dim3(kBlock), 0, st, W1, W2, hidden_pre, prob, target,
+                           mode, act, make_drop(p_drop, call_id, Hd), rng_state, grad_loss, (int)B, (int)C, (int)Hd, (int)K, dh_ws,
+                           a_ws, dpooled, lddp, class_weight, pos_weight);
+        hipLaunchKernelGGL(head_mlp_bwd_weights_kernel<true>, dim3((unsigned)(K + Hd)), dim3(kBlock), 0, st, pooled, ldp, prob,
+                           target, mode, grad_loss, (int)B, (int)C, (int)Hd, (int)K, dh_ws, a_ws, dW1, db1, dW2, db2, accumulate,
+                           class_weight, pos_weight);
+        return launch_status("glass_head_mlp_loss_bwd_w_f32");
+    }
+    hipLaunchKernelGGL(head_mlp_bwd_rows_kernel<false>, dim3((unsigned)B), dim3(kBlock), 0, st, W1, W2, hidden_pre, prob, target, mode,
+                       act, make_drop(p_drop, call_id, Hd), rng_state, grad_loss, (int)B, (int)C, (int)Hd, (int)K, dh_ws, a_ws,
+                       dpooled, lddp, (const float*)nullptr, (const float*)nullptr);
+    hipLaunchKernelGGL(head_mlp_bwd_weights_kernel<false>, dim3((unsigned)(K + Hd)), dim3(kBlock), 0, st, pooled, ldp, prob, target,
+                       mode, grad_loss, (int)B, (int)C, (int)Hd, (int)K, dh_ws, a_ws, dW1, db1, dW2, db2, accumulate,
+                       (const float*)nullptr, (const float*)nullptr);
+    return launch_status("glass_head_mlp_loss_bwd_f32");
 }
 
 extern "C" int glass_head_mlp_loss_bwd_f32(const float* pooled, int64_t ldp, const float* W1, const float* W2,
@@ -249,20 +337,9 @@ extern "C" int glass_head_mlp_loss_bwd_f32(const float* pooled, int64_t ldp, con
                                            float p_drop, const uint64_t* rng_state, uint64_t call_id, const float* grad_loss,
                                            int64_t B, int64_t C, int64_t Hd, int64_t K, float* ws, float* dpooled, int64_t lddp,
                                            float* dW1, float* db1, float* dW2, float* db2, int accumulate, void* stream) {
-    GLASS_REQUIRE(pooled && W1 && W2 && hidden_pre && prob && target && grad_loss && ws && dpooled && dW1 && db1 && dW2 && db2,
-                  "head_mlp_loss_bwd: null pointer");
-    GLASS_REQUIRE(mlp_drop_ok(p_drop, rng_state), "head_mlp_loss_bwd: dropout needs 0 <= p < 1 and the rng words");
-    if (int rc = mlp_check("head_mlp_loss_bwd", mode, act, B, C, Hd, K, ldp)) return rc;
-    GLASS_REQUIRE(lddp >= C, "head_mlp_loss_bwd: lddp < C");
-    float* dh_ws = ws;            // [B, Hd]
-    float* a_ws = ws + B * Hd;    // [B, Hd]
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(head_mlp_bwd_rows_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, W1, W2, hidden_pre, prob, target, mode,
-                       act, make_drop(p_drop, call_id, Hd), rng_state, grad_loss, (int)B, (int)C, (int)Hd, (int)K, dh_ws, a_ws,
-                       dpooled, lddp);
-    hipLaunchKernelGGL(head_mlp_bwd_weights_kernel, dim3((unsigned)(K + Hd)), dim3(kBlock), 0, st, pooled, ldp, prob, target,
-                       mode, grad_loss, (int)B, (int)C, (int)Hd, (int)K, dh_ws, a_ws, dW1, db1, dW2, db2, accumulate);
-    return launch_status("glass_head_mlp_loss_bwd_f32");
+    return glass_head_mlp_loss_bwd_w_f32(pooled, ldp, W1, W2, hidden_pre, prob, target, mode, act, p_drop, rng_state, call_id,
+                                         grad_loss, B, C, Hd, K, ws, dpooled, lddp, dW1, db1, dW2, db2, accumulate, nullptr,
+                                         nullptr, stream);
 }
 
 extern "C" int glass_head_mlp_f32(const float* pooled, int64_t ldp, const float* W1, const float* b1, const float* W2,
@@ -273,8 +350,9 @@ extern "C" int glass_head_mlp_f32(const float* pooled, int64_t ldp, const float*
     GLASS_REQUIRE(ldl >= K, "head_mlp: ldl < K");
     int stage;
     const size_t lds = mlp_fwd_lds(C, Hd, &stage);
-    hipLaunchKernelGGL(head_mlp_fwd_kernel<false>, dim3((unsigned)B), dim3(kBlock), lds, (hipStream_t)stream, pooled, ldp, W1,
+    hipLaunchKernelGGL((head_mlp_fwd_kernel<false, false>), dim3((unsigned)B), dim3(kBlock), lds, (hipStream_t)stream, pooled, ldp, W1,
                        b1, W2, b2, (const void*)nullptr, GLASS_LOSS_CE, act, make_drop(0.f, 0, Hd), (const uint64_t*)nullptr, (int)C,
-                       (int)Hd, (int)K, stage, (float*)nullptr, logits, ldl, (float*)nullptr, (float*)nullptr);
+                       (int)Hd, (int)K, stage, (float*)nullptr, logits, ldl, (float*)nullptr, (float*)nullptr,
+                       (const float*)nullptr, (const float*)nullptr);
     return launch_status("glass_head_mlp_f32");
 }

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "gn_math.h"
 #include "gn_acc.h"
+#include "head_loss.h"
 
 namespace glass {
 
@@ -89,6 +90,7 @@ struct R1Args {
     int stash;           // != 0: the padded row's node ids are staged in LDS (Smax ints behind the other arrays) by the counting pass
     long long* bwd_acc;  // != nullptr: the subgraph's share of the two backward column sums goes to exact accumulators
     int bwd_rep;         // (the backfill launch folds them: no reduce launch in between)
+    const float *cw, *pw;  // weighted losses (head_loss.h): class weights of cross-entropy / pos_weight of BCE, nullable (WT)
 };
 
 // dynamic LDS (floats): sums[2C doubles] | coef_s[2C] | mu_rstd_s[2C] | pooled_s[C] | xh_s[C] | (MAX: arg_s[C]) |
@@ -102,7 +104,10 @@ struct R1Args {
 constexpr int readout_lds_head(bool mx) { return mx ? 11 : 10; }  // C-sized float arrays in front of red
 constexpr int readout_red_stride(bool mx) { return mx ? 12 : 8; }  // floats per thread in red (MAX: + 4 argmax lanes)
 
-template <int VW, bool MAX>
+// WT: the weighted losses.  With class weights d logits needs the batch's weight sum inside this launch: every workgroup
+// recomputes it from target and cw (head_loss.h: ce_weight_sum, B loads) — no launch, no float atomic, the same bits in every
+// workgroup and in the mean role behind.  The entries launch WT = false when both pointers are null.
+template <int VW, bool MAX, bool WT>
 __global__ __launch_bounds__(kBlock) void readout_subgraph_kernel(R1Args a) {
     extern __shared__ float sm[];
     const int C = a.C, K = a.K;
@@ -311,7 +316,34 @@ __global__ __launch_bounds__(kBlock) void readout_subgraph_kernel(R1Args a) {
     }
     __syncthreads();
     // ---- loss term and d logits (mean reduction over B rows, or B*K elements for BCE) ----
-    if (tid == 0) {
+    [[maybe_unused]] float wscale = 0.f;  // (WT) grad_loss / the denominator of the weighted loss
+    if constexpr (WT)  // red is free since the pooling's last barrier; its first 8-byte aligned kBlock doubles
+        wscale = head_loss_scale(a.gl, a.loss_mode, a.B, K, a.cw, a.target,
+                                 reinterpret_cast<double*>(red + ((readout_lds_head(MAX) * C) & 1)));
+    if constexpr (WT) {
+        if (tid == 0) {
+            float term = 0.f;
+            if (a.loss_mode == kLossCE) {
+                float m = zs[0];
+                for (int k = 1; k < K; ++k) m = fmaxf(m, zs[k]);
+                float se = 0.f;
+                for (int k = 0; k < K; ++k) se += expf(zs[k] - m);
+                const float lse = m + logf(se);
+                const int64_t t = ((const int64_t*)a.target)[b];
+                const float wt = a.cw ? ce_class_weight(a.cw, t, K) : 1.f;
+                for (int k = 0; k < K; ++k) dl[k] = wscale * wt * (expf(zs[k] - lse) - (t == k ? 1.f : 0.f));
+                term = (t >= 0 && t < K) ? wt * (lse - zs[t]) : 0.f;
+            } else {
+                const float* y = (const float*)a.target + (int64_t)b * K;
+                for (int k = 0; k < K; ++k) {
+                    const float z = zs[k], p = a.pw ? a.pw[k] : 1.f;
+                    dl[k] = wscale * bce_pw_grad(1.f / (1.f + expf(-z)), y[k], p);
+                    term += bce_pw_term(z, y[k], p);
+                }
+            }
+            a.ws.loss_rows[b] = term;
+        }
+    } else if (tid == 0) {
         const float gscale = a.gl[0] / (a.loss_mode == kLossCE ? (float)a.B : (float)a.B * (float)K);
         float term = 0.f;
         if (a.loss_mode == kLossCE) {
@@ -367,6 +399,7 @@ struct R2Args {
     int64_t n_nodes;
     const float *gamma, *alpha, *saved;
     float *dgamma, *dbeta, *dalpha; int acc_gn;
+    const float* cw; const void* target;  // weighted cross-entropy (cw != nullptr): the mean divides by the batch's weight sum
 };
 
 // blocks [0,K): head gradient row k;  block K: mean loss;  blocks (K, K + ceil(C/4)]: GraphNorm backward finalize.
@@ -393,6 +426,8 @@ __global__ __launch_bounds__(kBlock) void readout_reduce_kernel(R2Args a) {
         return;
     }
     if (blk == a.K) {
+        double wsum = 0.0;
+        if (a.cw) wsum = ce_weight_sum(a.cw, (const int64_t*)a.target, a.B, a.K, smd);
         double part = 0.0;
         for (int b = tid; b < a.B; b += kBlock) part += (double)a.ws.loss_rows[b];
         smd[tid] = part;
@@ -402,7 +437,7 @@ __global__ __launch_bounds__(kBlock) void readout_reduce_kernel(R2Args a) {
             __syncthreads();
         }
         if (tid == 0) {
-            const float l = (float)(smd[0] / (a.loss_mode == kLossCE ? (double)a.B : (double)a.B * (double)a.K));
+            const float l = (float)(smd[0] / (a.cw ? wsum : a.loss_mode == kLossCE ? (double)a.B : (double)a.B * (double)a.K));
             a.loss[0] = l;
             if (a.loss_sum) a.loss_sum[0] += l;
         }
@@ -549,6 +584,7 @@ struct BackfillFin {
     float *dWh, *dbh, *loss;
     int B, K, loss_mode, acc_head;
     float* loss_sum;  // nullable: += the step's loss
+    const float* cw; const void* target;  // weighted cross-entropy (cw != nullptr): the mean divides by the batch's weight sum
 };
 
 template <bool MAX>
@@ -582,12 +618,14 @@ __global__ __launch_bounds__(kOrdBlock) void readout_backfill_kernel(const float
                 fin.dbh[blk] = fin.acc_head ? fin.dbh[blk] + sum : sum;
             }
         } else if (tid < kWave) {  // mean loss: one wave, fixed order
+            double wsum = 0.0;
+            if (fin.cw) wsum = ce_weight_sum_wave(fin.cw, (const int64_t*)fin.target, fin.B, fin.K, tid);
             double part = 0.0;
             for (int b = tid; b < fin.B; b += kWave) part += (double)fin.loss_rows[b];
 #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) part += __shfl_xor(part, o);
             if (tid == 0) {
-                const float l = (float)(part / (fin.loss_mode == kLossCE ? (double)fin.B : (double)fin.B * (double)fin.K));
+                const float l = (float)(part / (fin.cw ? wsum : fin.loss_mode == kLossCE ? (double)fin.B : (double)fin.B * (double)fin.K));
                 fin.loss[0] = l;
                 if (fin.loss_sum) fin.loss_sum[0] += l;
             }
@@ -860,7 +898,7 @@ static int readout_train(const char* what, const float* jk, int64_t ldj, const f
                          float* dalpha, int acc_gn, void* ws, int64_t n_nodes, int64_t C,
                          const uint8_t* mask, const int32_t* lab_rows, const int32_t* lab_count,
                          const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
-                         float* loss_sum, void* stream) {
+                         float* loss_sum, const float* class_weight, const float* pos_weight, void* stream) {
     GLASS_REQUIRE(jk && gn_saved && gamma && alpha && pos && Wh && bh && target && grad_loss && pooled && logits && loss &&
                       djk && dWh && dbh && ws,
                   "readout_train: null pointer");
@@ -870,6 +908,10 @@ static int readout_train(const char* what, const float* jk, int64_t ldj, const f
         (loss_mode != kLossCE && loss_mode != kLossBCE)) {
         set_error("readout_train: unsupported shape/mode (C=%lld K=%lld pool=%d loss=%d): C %% 4 == 0, C <= 1024, "
                   "K <= 256, pool sum|mean|size (max: glass_readout_max_train_f32)", (long long)C, (long long)K, pool_mode, loss_mode);
+        return GLASS_E_UNSUPPORTED;
+    }
+    if (!loss_weights_ok(loss_mode, class_weight, pos_weight)) {
+        set_error("readout_train: class_weight goes with cross-entropy, pos_weight with BCE, at most one of them");
         return GLASS_E_UNSUPPORTED;
     }
     const bool vec = C % 4 == 0 && ldj % 4 == 0 && lddj % 4 == 0 && aligned16(jk) && aligned16(djk) && aligned16(pooled);
@@ -905,14 +947,19 @@ static int readout_train(const char* what, const float* jk, int64_t ldj, const f
     const int stash = Smax > 2 * (kBlock >> tc_log2) && n_nodes < (1ll << 31) && lds1_base + sizeof(float) * (size_t)Smax <= 64 * 1024;
     R1Args a1{jk, ldj, gn_saved, alpha, pos, (int)Smax, pool_mode, Wh, bh, target, loss_mode, (int)B, (int)C, (int)K,
               grad_loss, pooled, logits, w, n_nodes, tc_log2, esrc, stash, two ? reinterpret_cast<long long*>(gn_bwd_acc) : nullptr,
-              gn_bwd_rep};
+              gn_bwd_rep, class_weight, pos_weight};
     const size_t lds1 = lds1_base + sizeof(float) * (size_t)(stash ? Smax : 0);
-    if (vec)
-        hipLaunchKernelGGL((readout_subgraph_kernel<4, MAX>), dim3((unsigned)B), dim3(kBlock), lds1, st, a1);
+    const bool wt = class_weight || pos_weight;
+    if (vec && wt)
+        hipLaunchKernelGGL((readout_subgraph_kernel<4, MAX, true>), dim3((unsigned)B), dim3(kBlock), lds1, st, a1);
+    else if (vec)
+        hipLaunchKernelGGL((readout_subgraph_kernel<4, MAX, false>), dim3((unsigned)B), dim3(kBlock), lds1, st, a1);
+    else if (wt)
+        hipLaunchKernelGGL((readout_subgraph_kernel<1, MAX, true>), dim3((unsigned)B), dim3(kBlock), lds1, st, a1);
     else
-        hipLaunchKernelGGL((readout_subgraph_kernel<1, MAX>), dim3((unsigned)B), dim3(kBlock), lds1, st, a1);
+        hipLaunchKernelGGL((readout_subgraph_kernel<1, MAX, false>), dim3((unsigned)B), dim3(kBlock), lds1, st, a1);
     R2Args a2{pooled, w, (int)B, (int)C, (int)K, loss_mode, dWh, dbh, acc_head, loss, loss_sum, n_nodes, gamma, alpha, gn_saved,
-              dgamma, dbeta, dalpha, acc_gn};
+              dgamma, dbeta, dalpha, acc_gn, class_weight, target};
     size_t lds2 = sizeof(double) * kBlock * 2;
     if (sizeof(float) * (size_t)B > lds2) lds2 = sizeof(float) * (size_t)B;
     GLASS_REQUIRE(lds2 <= 64 * 1024, "readout_train: batch too large for the LDS staging");
@@ -933,7 +980,8 @@ static int readout_train(const char* what, const float* jk, int64_t ldj, const f
         unsigned extra = 0;
         if (two) {
             fin = BackfillFin{reinterpret_cast<const long long*>(gn_bwd_acc), gn_bwd_rep, gamma, alpha, gn_saved, dgamma, dbeta, dalpha,
-                              acc_gn, pooled, w.dlogits, w.loss_rows, dWh, dbh, loss, (int)B, (int)K, loss_mode, acc_head, loss_sum};
+                              acc_gn, pooled, w.dlogits, w.loss_rows, dWh, dbh, loss, (int)B, (int)K, loss_mode, acc_head, loss_sum,
+                              class_weight, target};
             lds3 = sizeof(int32_t) * (size_t)((B * Smax + 1) & ~1ll) + sizeof(double) * 2 * (size_t)C + sizeof(float) * 3 * (size_t)C;
             if (lds3 < sizeof(float) * (size_t)B) lds3 = sizeof(float) * (size_t)B;
             extra = (unsigned)K + 1;
@@ -968,7 +1016,21 @@ static int readout_train(const char* what, const float* jk, int64_t ldj, const f
 #define GLASS_READOUT_ARGS                                                                                                   \
     jk, ldj, gn_saved, gamma, alpha, pos, B, Smax, pool_mode, Wh, bh, target, loss_mode, K, grad_loss, pooled, logits, loss, \
         djk, lddj, dWh, dbh, acc_head, dgamma, dbeta, dalpha, acc_gn, ws, n_nodes, C, mask, lab_rows, lab_count, gn_src,     \
-        gn_bwd_acc, gn_bwd_rep, scatter_ws, loss_sum, stream
+        gn_bwd_acc, gn_bwd_rep, scatter_ws, loss_sum, class_weight, pos_weight, stream
+
+extern "C" int glass_readout_train_w_f32(const float* jk, int64_t ldj, const float* gn_saved, const float* gamma,
+                                       const float* alpha, const int64_t* pos, int64_t B, int64_t Smax, int pool_mode,
+                                       const float* Wh, const float* bh, const void* target, int loss_mode, int64_t K,
+                                       const float* grad_loss, float* pooled, float* logits, float* loss, float* djk,
+                                       int64_t lddj, float* dWh, float* dbh, int acc_head, float* dgamma, float* dbeta,
+                                       float* dalpha, int acc_gn, void* ws, int64_t n_nodes, int64_t C,
+                                       const uint8_t* mask, const int32_t* lab_rows, const int32_t* lab_count,
+                                       const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
+                                       float* loss_sum, const float* class_weight, const float* pos_weight,
+                                         void* stream) {
+    return readout_train<false>("glass_readout_train_w_f32", GLASS_READOUT_ARGS);
+}
+
 
 extern "C" int glass_readout_train_f32(const float* jk, int64_t ldj, const float* gn_saved, const float* gamma,
                                        const float* alpha, const int64_t* pos, int64_t B, int64_t Smax, int pool_mode,
@@ -979,7 +1041,22 @@ extern "C" int glass_readout_train_f32(const float* jk, int64_t ldj, const float
                                        const uint8_t* mask, const int32_t* lab_rows, const int32_t* lab_count,
                                        const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
                                        float* loss_sum, void* stream) {
+    const float *class_weight = nullptr, *pos_weight = nullptr;
     return readout_train<false>("glass_readout_train_f32", GLASS_READOUT_ARGS);
+}
+
+extern "C" int glass_readout_max_train_w_f32(const float* jk, int64_t ldj, const float* gn_saved, const float* gamma,
+                                           const float* alpha, const int64_t* pos, int64_t B, int64_t Smax,
+                                           const float* Wh, const float* bh, const void* target, int loss_mode, int64_t K,
+                                           const float* grad_loss, float* pooled, float* logits, float* loss, float* djk,
+                                           int64_t lddj, float* dWh, float* dbh, int acc_head, float* dgamma, float* dbeta,
+                                           float* dalpha, int acc_gn, void* ws, int64_t n_nodes, int64_t C,
+                                           const uint8_t* mask, const int32_t* lab_rows, const int32_t* lab_count,
+                                           const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
+                                           float* loss_sum, const float* class_weight, const float* pos_weight,
+                                         void* stream) {
+    const int pool_mode = GLASS_POOL_MAX;
+    return readout_train<true>("glass_readout_max_train_w_f32", GLASS_READOUT_ARGS);
 }
 
 extern "C" int glass_readout_max_train_f32(const float* jk, int64_t ldj, const float* gn_saved, const float* gamma,
@@ -991,6 +1068,7 @@ extern "C" int glass_readout_max_train_f32(const float* jk, int64_t ldj, const f
                                            const uint8_t* mask, const int32_t* lab_rows, const int32_t* lab_count,
                                            const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
                                            float* loss_sum, void* stream) {
+    const float *class_weight = nullptr, *pos_weight = nullptr;
     const int pool_mode = GLASS_POOL_MAX;
     return readout_train<true>("glass_readout_max_train_f32", GLASS_READOUT_ARGS);
 }

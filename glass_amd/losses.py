@@ -7,26 +7,54 @@ and, when the model's head is a bare nn.Linear (GLASSTest.py:159-160), runs head
 (`glass_head_loss_fwd/bwd_f32`) instead of ~12 launches.  The reference's other head, the two-layer `models.MLP` of GNN-seg
 and GNNEmb (Linear -> Dropout -> activation -> Linear), is recognised by `fusable_head` and runs with its loss and their
 backward as four launches (`mlp_head_loss`, `glass_head_mlp_loss_fwd/bwd_f32`); DESIGN.md has the launch counts measured
-with and without it."""
+with and without it.  `CrossEntropy(weight=)` / `BCEWithLogits(pos_weight=)` carry class weights into the same launches
+(`fusable_spec`, the `_w` entries of the C ABI; `balanced_weights` is the drivers' `--class_weight balanced`)."""
 import torch
 import torch.nn as nn
 
 from . import _lib, ops
 
 
+def _checked_weight(w, what):
+    """A weight vector the kernels can take: a 1-D fp32 tensor, every value finite and > 0 (ValueError otherwise)."""
+    if not (isinstance(w, torch.Tensor) and w.dim() == 1 and w.numel() > 0 and w.dtype == torch.float32):
+        raise ValueError(f"{what}: a non-empty 1-D float32 tensor expected, got "
+                         f"{tuple(w.shape)} {w.dtype}" if isinstance(w, torch.Tensor) else f"{what}: a tensor expected, got {type(w).__name__}")
+    if not bool((torch.isfinite(w) & (w > 0)).all()):
+        raise ValueError(f"{what}: every value must be finite and greater than 0")
+    return w.detach().clone().contiguous()
+
+
 class CrossEntropy(nn.Module):
+    """CrossEntropyLoss(weight=weight), mean reduction.  weight (optional): one fp32 value per class, finite and > 0 — kept
+    as a buffer (it follows .to(device)); the fused heads and the captured step read it on the device (`fusable_spec`)."""
     mode = 0
 
+    def __init__(self, weight=None):
+        super().__init__()
+        self.register_buffer("weight", None if weight is None else _checked_weight(weight, "CrossEntropy(weight=)"))
+
     def forward(self, pred, y):
-        return nn.functional.cross_entropy(pred, y)
+        return nn.functional.cross_entropy(pred, y, weight=self.weight)
 
 
 class BCEWithLogits(nn.Module):
-    """Binary / multi-label: BCEWithLogitsLoss()(pred.flatten(), y.flatten())."""
+    """Binary / multi-label: BCEWithLogitsLoss(pos_weight=pos_weight)(pred.flatten(), y.flatten()) — pos_weight (optional):
+    one fp32 value per output column, finite and > 0, kept as a buffer."""
     mode = 1
 
+    def __init__(self, pos_weight=None):
+        super().__init__()
+        self.register_buffer("pos_weight",
+                             None if pos_weight is None else _checked_weight(pos_weight, "BCEWithLogits(pos_weight=)"))
+
     def forward(self, pred, y):
-        return nn.functional.binary_cross_entropy_with_logits(pred.flatten(), y.flatten())
+        if self.pos_weight is None:
+            return nn.functional.binary_cross_entropy_with_logits(pred.flatten(), y.flatten())
+        # (one weight per output column: applied on [B, K], the mean over B*K elements as on the flattened tensors)
+        K = self.pos_weight.numel()
+        return nn.functional.binary_cross_entropy_with_logits(pred.reshape(-1, K), y.reshape(-1, K).to(pred.dtype),
+                                                              pos_weight=self.pos_weight)
 
 
 import os as _os
@@ -84,7 +112,7 @@ def fusable_mode(loss_fn):
     case is a lambda around BCEWithLogitsLoss (GLASSTest.py:57-58) — is recognised by what it computes (`_probe`, once per
     callable)."""
     if isinstance(loss_fn, (CrossEntropy, BCEWithLogits)):
-        return loss_fn.mode
+        return loss_fn.mode  # (a marker's weights are `fusable_spec`'s business: every consumer asks that)
     if (type(loss_fn) is nn.CrossEntropyLoss and loss_fn.weight is None and loss_fn.reduction == "mean" and
             loss_fn.ignore_index == -100 and getattr(loss_fn, "label_smoothing", 0.0) == 0.0):
         return 0
@@ -115,6 +143,94 @@ def fusable_mode(loss_fn):
     return mode
 
 
+def fusable_spec(loss_fn):
+    """(mode, class_weight, pos_weight) when the training step can fuse this loss with the head, else None — what every
+    consumer asks (stack, step.TrainStep, head_loss / mlp_head_loss, the GNN-seg model): mode as `fusable_mode`, and the
+    weight tensors of this module's marker classes (at most one of them set; None: unweighted).  Weights come from the
+    marker classes ONLY: torch's own weighted losses and opaque callables around them stay None — the probe compares a
+    callable with the unweighted losses, and no number of evaluations would tell which tensor object holds its weights, so
+    the captured step could not follow them."""
+    mode = fusable_mode(loss_fn)
+    if mode is None:
+        return None
+    if isinstance(loss_fn, CrossEntropy):
+        return mode, loss_fn.weight, None
+    if isinstance(loss_fn, BCEWithLogits):
+        return mode, None, loss_fn.pos_weight
+    return mode, None, None
+
+
+def on_device(loss_fn, device):
+    """A marker loss whose weight buffer lives elsewhere is moved to `device` (in place, as nn.Module.to does): the fused
+    kernels and the eager loss both read it there.  Anything else is returned as it is."""
+    if isinstance(loss_fn, (CrossEntropy, BCEWithLogits)):
+        w = loss_fn.weight if isinstance(loss_fn, CrossEntropy) else loss_fn.pos_weight
+        if w is not None and w.device != torch.device(device):
+            loss_fn.to(device)
+    return loss_fn
+
+
+def balanced_weights(y, n_class=None):
+    """The `--class_weight balanced` vector of the drivers, from the TRAINING split's targets only (fp32, CPU).
+    Multi-class (integer y [n]): w_k = n / (K * count_k), K = n_class (default max + 1) -> CrossEntropy(weight=).
+    Binary / multi-label (floating y [n] or [n, K]): p_k = neg_k / pos_k per column -> BCEWithLogits(pos_weight=).
+    A class or column with a zero count (no sample, or for p_k no positive or no negative) gets 1."""
+    y = y.detach().cpu()
+    if not y.is_floating_point():
+        y = y.reshape(-1).to(torch.int64)
+        K = int(n_class) if n_class is not None else int(y.max()) + 1
+        count = torch.bincount(y[(y >= 0) & (y < K)], minlength=K).to(torch.float64)
+        w = torch.where(count > 0, float(y.numel()) / (K * count.clamp(min=1.0)), torch.ones_like(count))
+        return w.to(torch.float32)
+    y2 = y.reshape(y.shape[0], -1).to(torch.float64)
+    pos = (y2 > 0.5).sum(dim=0).to(torch.float64)
+    neg = float(y2.shape[0]) - pos
+    p = torch.where((pos > 0) & (neg > 0), neg / pos.clamp(min=1.0), torch.ones_like(pos))
+    return p.to(torch.float32)
+
+
+def balanced_loss(y_train, n_out):
+    """The marker loss with `balanced_weights` of the training targets: CrossEntropy(weight=) over n_out classes for integer
+    targets, BCEWithLogits(pos_weight=) for floating ones (binary / multi-label, n_out columns)."""
+    if not y_train.is_floating_point():
+        return CrossEntropy(weight=balanced_weights(y_train, n_out))
+    return BCEWithLogits(pos_weight=balanced_weights(y_train))
+
+
+def _spec(mode):
+    """A consumer's `mode` argument: the plain mode number (unweighted) or a fusable_spec tuple."""
+    return (mode, None, None) if isinstance(mode, int) else tuple(mode)
+
+
+def weight_ptrs(spec, K, device):
+    """(class_weight pointer, pos_weight pointer) of a spec for a head of K outputs on `device` (0: not set), checked before
+    any launch: the length is K and the tensor is fp32, contiguous and on the device (ValueError otherwise)."""
+    out = []
+    for w, what in ((spec[1], "class weight"), (spec[2], "pos_weight")):
+        if w is None:
+            out.append(0)
+            continue
+        if w.dim() != 1 or w.numel() != K:
+            raise ValueError(f"{what}: {w.numel()} values for a head of {K} outputs")
+        if w.dtype != torch.float32 or not w.is_contiguous() or w.device != torch.device(device):
+            raise ValueError(f"{what}: a contiguous float32 tensor on {device} expected (move the loss with .to(device)), "
+                             f"got {w.dtype} on {w.device}")
+        out.append(w.data_ptr())
+    return tuple(out)
+
+
+def _functional_loss(logits, target, spec):
+    """torch's functional form of a spec (the module paths: sizes the kernels refuse, tensors not fp32 on the GPU)."""
+    mode, cw, pw = spec
+    if mode == 0:
+        return nn.functional.cross_entropy(logits, target, weight=cw)
+    if pw is None:
+        return nn.functional.binary_cross_entropy_with_logits(logits.flatten(), target.flatten().to(logits.dtype))
+    K = pw.numel()
+    return nn.functional.binary_cross_entropy_with_logits(logits.reshape(-1, K), target.reshape(-1, K).to(logits.dtype),
+                                                          pos_weight=pw)
+
+
 class HeadLossFn(torch.autograd.Function):
     """loss = L(pooled @ W^T + b, target) — forward in one launch, backward in one launch."""
     @staticmethod
@@ -123,17 +239,21 @@ class HeadLossFn(torch.autograd.Function):
         pooled, ldp = ops._rows(pooled)
         B, C = pooled.shape
         K = weight.shape[0]
+        spec = _spec(mode)
+        mode = spec[0]
+        wptrs = weight_ptrs(spec, K, pooled.device)
         w, b = weight.contiguous(), bias.contiguous()
         tgt = target.contiguous().to(torch.int64 if mode == 0 else torch.float32)
         logits = torch.empty((B, K), dtype=torch.float32, device=pooled.device)
         prob = torch.empty(B * K + B, dtype=torch.float32, device=pooled.device)  # probabilities + per-row loss terms
         loss = torch.empty((), dtype=torch.float32, device=pooled.device)
-        rc = _lib.load().glass_head_loss_fwd_f32(pooled.data_ptr(), ldp, w.data_ptr(), b.data_ptr(), tgt.data_ptr(), mode,
-                                                 B, C, K, logits.data_ptr(), prob.data_ptr(), loss.data_ptr(),
-                                                 ops._stream())
-        _lib.check(rc, "glass_head_loss_fwd_f32")
+        rc = _lib.load().glass_head_loss_fwd_w_f32(pooled.data_ptr(), ldp, w.data_ptr(), b.data_ptr(), tgt.data_ptr(), mode,
+                                                   B, C, K, logits.data_ptr(), prob.data_ptr(), loss.data_ptr(), *wptrs,
+                                                   ops._stream())
+        _lib.check(rc, "glass_head_loss_fwd_w_f32")
         ctx.save_for_backward(pooled, w, prob, tgt)
         ctx.cfg = (mode, B, C, K)
+        ctx.wspec = spec  # (keeps the weight tensors alive until the backward has read them)
         # direct: accumulate dW / db straight into the flat gradient arena (weight.grad / bias.grad views)
         ctx.direct = (weight, bias) if (direct and weight.grad is not None and bias.grad is not None) else None
         ctx.mark_non_differentiable(logits)
@@ -150,17 +270,19 @@ class HeadLossFn(torch.autograd.Function):
             dW, db, acc = ctx.direct[0].grad, ctx.direct[1].grad, 1
         else:
             dW, db, acc = torch.empty_like(w), torch.empty(K, dtype=torch.float32, device=w.device), 0
-        rc = _lib.load().glass_head_loss_bwd_f32(pooled.data_ptr(), pooled.stride(0), w.data_ptr(), prob.data_ptr(),
-                                                 tgt.data_ptr(), mode, gl.data_ptr(), B, C, K, dpooled.data_ptr(), C,
-                                                 dW.data_ptr(), db.data_ptr(), acc, ops._stream())
-        _lib.check(rc, "glass_head_loss_bwd_f32")
+        rc = _lib.load().glass_head_loss_bwd_w_f32(pooled.data_ptr(), pooled.stride(0), w.data_ptr(), prob.data_ptr(),
+                                                   tgt.data_ptr(), mode, gl.data_ptr(), B, C, K, dpooled.data_ptr(), C,
+                                                   dW.data_ptr(), db.data_ptr(), acc, *weight_ptrs(ctx.wspec, K, pooled.device),
+                                                   ops._stream())
+        _lib.check(rc, "glass_head_loss_bwd_w_f32")
         if ctx.direct is not None:
             return dpooled, None, None, None, None, None
         return dpooled, dW, db, None, None, None
 
 
 def head_loss(pooled, linear, target, mode, direct=False):
-    """-> (loss, logits) for an nn.Linear head; mode 0 = cross-entropy, 1 = BCE-with-logits."""
+    """-> (loss, logits) for an nn.Linear head; mode 0 = cross-entropy, 1 = BCE-with-logits — or a `fusable_spec` tuple,
+    whose weights the kernels then apply (their length must be the head's K: ValueError before any launch)."""
     return HeadLossFn.apply(pooled, linear.weight, linear.bias, target, mode, direct)
 
 
@@ -215,6 +337,9 @@ class MLPHeadLossFn(torch.autograd.Function):
         pooled, ldp = ops._rows(pooled)
         B, C = pooled.shape
         Hd, K = w1.shape[0], w2.shape[0]
+        spec = _spec(mode)
+        mode = spec[0]
+        wptrs = weight_ptrs(spec, K, pooled.device)
         if w1.shape[1] != C or w2.shape[1] != Hd or any(t.dtype != torch.float32 for t in (w1, b1, w2, b2)):
             raise _lib.GlassHipError(f"MLP head: fp32 weights [Hd,{C}] and [K,Hd] expected, got {tuple(w1.shape)} {w1.dtype}, "
                                      f"{tuple(w2.shape)} {w2.dtype}")
@@ -226,14 +351,15 @@ class MLPHeadLossFn(torch.autograd.Function):
         logits = torch.empty((B, K), dtype=torch.float32, device=dev)
         prob = torch.empty(B * K + B, dtype=torch.float32, device=dev)  # probabilities + per-row loss terms
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        rc = _lib.load().glass_head_mlp_loss_fwd_f32(pooled.data_ptr(), ldp, w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(),
-                                                     b2c.data_ptr(), tgt.data_ptr(), mode, act, p_drop,
-                                                     0 if rng is None else rng.data_ptr(), HEAD_MLP_CALL_ID, B, C, Hd, K,
-                                                     hidden.data_ptr(), logits.data_ptr(), prob.data_ptr(), loss.data_ptr(),
-                                                     ops._stream())
+        rc = _lib.load().glass_head_mlp_loss_fwd_w_f32(pooled.data_ptr(), ldp, w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(),
+                                                       b2c.data_ptr(), tgt.data_ptr(), mode, act, p_drop,
+                                                       0 if rng is None else rng.data_ptr(), HEAD_MLP_CALL_ID, B, C, Hd, K,
+                                                       hidden.data_ptr(), logits.data_ptr(), prob.data_ptr(), loss.data_ptr(),
+                                                       *wptrs, ops._stream())
         if rc == -3:  # GLASS_E_UNSUPPORTED
             raise _HeadUnsupported(_lib.load().glass_last_error_string().decode(errors="replace"))
-        _lib.check(rc, "glass_head_mlp_loss_fwd_f32")
+        _lib.check(rc, "glass_head_mlp_loss_fwd_w_f32")
+        ctx.wspec = spec  # (keeps the weight tensors alive until the backward has read them)
         ctx.save_for_backward(pooled, w1c, w2c, hidden, prob, tgt)
         ctx.cfg = (mode, act, p_drop, B, C, Hd, K, ldp)
         ctx.rng = rng
@@ -256,12 +382,13 @@ class MLPHeadLossFn(torch.autograd.Function):
         else:
             grads, acc = [torch.empty_like(w1), torch.empty(Hd, dtype=torch.float32, device=dev), torch.empty_like(w2),
                           torch.empty(K, dtype=torch.float32, device=dev)], 0
-        rc = _lib.load().glass_head_mlp_loss_bwd_f32(pooled.data_ptr(), ldp, w1.data_ptr(), w2.data_ptr(),
-                                                     hidden.data_ptr(), prob.data_ptr(), tgt.data_ptr(), mode, act, p_drop,
-                                                     0 if ctx.rng is None else ctx.rng.data_ptr(), HEAD_MLP_CALL_ID,
-                                                     gl.data_ptr(), B, C, Hd, K, ws.data_ptr(), dpooled.data_ptr(), C,
-                                                     *(g.data_ptr() for g in grads), acc, ops._stream())
-        _lib.check(rc, "glass_head_mlp_loss_bwd_f32")
+        rc = _lib.load().glass_head_mlp_loss_bwd_w_f32(pooled.data_ptr(), ldp, w1.data_ptr(), w2.data_ptr(),
+                                                       hidden.data_ptr(), prob.data_ptr(), tgt.data_ptr(), mode, act, p_drop,
+                                                       0 if ctx.rng is None else ctx.rng.data_ptr(), HEAD_MLP_CALL_ID,
+                                                       gl.data_ptr(), B, C, Hd, K, ws.data_ptr(), dpooled.data_ptr(), C,
+                                                       *(g.data_ptr() for g in grads), acc,
+                                                       *weight_ptrs(ctx.wspec, K, pooled.device), ops._stream())
+        _lib.check(rc, "glass_head_mlp_loss_bwd_w_f32")
         if ctx.direct is not None:
             return (dpooled, ) + (None, ) * 10
         return (dpooled, *grads) + (None, ) * 6
@@ -269,19 +396,22 @@ class MLPHeadLossFn(torch.autograd.Function):
 
 def mlp_head_loss(pooled, mlp, target, mode, direct=False):
     """-> (loss, logits) for a two-layer models.MLP head (fusable_head(mlp) == "mlp2"); mode 0 = cross-entropy, 1 =
-    BCE-with-logits.  In training with dropout the mask comes from the device-resident counter stream (stream
+    BCE-with-logits — or a `fusable_spec` tuple, whose weights every path below applies (length K, else ValueError before
+    any launch).  In training with dropout the mask comes from the device-resident counter stream (stream
     HEAD_MLP_CALL_ID): this call reads a private snapshot of the (seed, step) words, in its forward and in its backward, and
     advances the live stream — a later training forward cannot pair this backward with another mask.  Same distribution as
     nn.Dropout's, other bits.  Sizes the kernels refuse (GLASS_E_UNSUPPORTED: more than 256 classes or 1024 hidden units) run
     as the modules, same semantics; so do tensors that are not fp32 on the GPU."""
     lin1, p, act, lin2 = _mlp2_parts(mlp)
     p = p if mlp.training else 0.0
+    spec = _spec(mode)
+    for w, what in ((spec[1], "class weight"), (spec[2], "pos_weight")):
+        if w is not None and w.numel() != lin2.out_features:
+            raise ValueError(f"{what}: {w.numel()} values for a head of {lin2.out_features} outputs")
 
     def modules():
         logits = mlp(pooled)
-        if mode == 0:
-            return nn.functional.cross_entropy(logits, target), logits
-        return nn.functional.binary_cross_entropy_with_logits(logits.flatten(), target.flatten().to(logits.dtype)), logits
+        return _functional_loss(logits, target, spec), logits
 
     params = (lin1.weight, lin1.bias, lin2.weight, lin2.bias)
     # the kernels are fp32 on the GPU: anything else (a half / double model, a CPU tensor) is the modules' business, as before
@@ -291,7 +421,7 @@ def mlp_head_loss(pooled, mlp, target, mode, direct=False):
     # leaves the stream alone.  (The first mask after ops.rng_seed is therefore drawn at step word 0.)
     rng = ops.rng_snapshot(pooled.device) if p > 0 else None
     try:
-        out = MLPHeadLossFn.apply(pooled, *params, target, mode, act, p, rng, direct)
+        out = MLPHeadLossFn.apply(pooled, *params, target, spec, act, p, rng, direct)
     except _HeadUnsupported:
         return modules()
     if rng is not None:

@@ -460,12 +460,12 @@ class GNN(nn.Module):
 
     def loss_and_logits(self, x, edge_index, edge_weight, subG_node, y, loss_fn):
         """-> (loss, logits) of one batch: forward up to the pool, then head + loss as four launches forward and
-        backward (losses.mlp_head_loss) when the loss is cross-entropy / BCE-with-logits (losses.fusable_mode) and the
+        backward (losses.mlp_head_loss) when the loss is cross-entropy / BCE-with-logits (losses.fusable_spec) and the
         head a two-layer MLP (losses.fusable_head); otherwise the head module and loss_fn(logits, y)."""
         from . import losses
         emb = self._pooled(x, edge_index, edge_weight, subG_node)
-        mode = losses.fusable_mode(loss_fn)
-        if mode is not None and losses.fusable_head(self.mods[1]) == "mlp2":
-            return losses.mlp_head_loss(emb, self.mods[1], y, mode)
+        spec = losses.fusable_spec(loss_fn)  # (mode, class weights, pos_weight): a weighted marker keeps its weights
+        if spec is not None and losses.fusable_head(self.mods[1]) == "mlp2":
+            return losses.mlp_head_loss(emb, self.mods[1], y, spec)
         logits = self.mods[1](emb)
         return loss_fn(logits, y), logits

@@ -727,6 +727,11 @@ class StackProgram:
         sws = ops._scratch(("readout_scatter", n, B, Smax), jk.device, sws_bytes).data_ptr() if sws_bytes > 0 else 0
         K = head.weight.shape[0]
         dev = jk.device
+        # loss_mode: the plain mode number, or a losses.fusable_spec tuple whose weights the readout applies
+        from . import losses
+        spec = losses._spec(loss_mode)
+        loss_mode = spec[0]
+        wptrs = losses.weight_ptrs(spec, K, dev)  # (ValueError before any launch: K values, fp32, on this device)
         f32 = dict(dtype=torch.float32, device=dev)
         acc_ro = st.get("gn_exact_readout")  # (the library takes the two-launch form only with the listed pooled rows)
         final = st["final_saved"]  # (kept alive across the call below: the glass_gn_src struct lives in it)
@@ -744,8 +749,8 @@ class StackProgram:
             labels = BatchLabels(n, pos.numel(), dev)
             labels.load(pos)
         largs = (0, 0, 0) if labels is None else (labels.mask.data_ptr(), labels.rows.data_ptr(), labels.count.data_ptr())
-        entry, name = ((lib.glass_readout_max_train_f32, "glass_readout_max_train_f32") if mx else
-                       (lib.glass_readout_train_f32, "glass_readout_train_f32"))
+        entry, name = ((lib.glass_readout_max_train_w_f32, "glass_readout_max_train_w_f32") if mx else
+                       (lib.glass_readout_train_w_f32, "glass_readout_train_w_f32"))
         mode_arg = () if mx else (_lib.POOL_MODES[pool_mode], )
         _check(entry(jk.data_ptr(), jk.stride(0), saved, gn.weight.data_ptr(),
                      gn.mean_scale.data_ptr(), pos.data_ptr(), B, Smax, *mode_arg,
@@ -755,7 +760,7 @@ class StackProgram:
                      head.bias.grad.data_ptr(), st["acc"], gn.weight.grad.data_ptr(),
                      gn.bias.grad.data_ptr(), gn.mean_scale.grad.data_ptr(), st["acc"], ws.data_ptr(),
                      n, C, *largs, src, 0 if acc_ro is None else acc_ro.data_ptr(), REP_DENSE, sws,
-                     0 if self.loss_sum is None else self.loss_sum.data_ptr(), _stream()),
+                     0 if self.loss_sum is None else self.loss_sum.data_ptr(), *wptrs, _stream()),
                name)
         st["djk"] = djk
         return loss, logits
@@ -962,7 +967,7 @@ def step_supported(model, loss_fn):
     if not (isinstance(pool, PoolModule) and pool.trans_fn is None and pool.mode in ("sum", "mean", "size", "max")):
         return False
     if not (type(head) is nn.Linear and head.bias is not None and head.weight.grad is not None and
-            head.bias.grad is not None and losses.fusable_mode(loss_fn) is not None):
+            head.bias.grad is not None and losses.fusable_spec(loss_fn) is not None):
         return False
     C = emb.gns[-1].weight.shape[0]
     lib, K = _lib.load(), head.weight.shape[0]
@@ -1008,7 +1013,7 @@ def loss_and_grads(model, loss_fn, x, edge_index, edge_weight, pos, z, target, o
             raise ValueError("z must be a tensor, None or 'pos'")
         z = ("pos", pos)
     return prog.loss_and_grads(x_flat, z, edge_index, edge_weight, pos, model.pools[0].mode, model.preds[0], target,
-                               losses.fusable_mode(loss_fn), overwrite, tail_hook, labels, fused_opt)
+                               losses.fusable_spec(loss_fn), overwrite, tail_hook, labels, fused_opt)
 
 
 def applied_optimizer(model):

@@ -40,7 +40,8 @@ class TrainStep:
         """preserve_state: the warm-up steps are run for their side effects only (CSR / plan / workspace / BLAS
         handle creation) and parameters, optimizer state and dropout stream are restored afterwards, so the
         training trajectory is exactly the one of a loop without warm-up (used by impl.train.train)."""
-        self.model, self.opt, self.loss_fn = model, optimizer, loss_fn
+        from . import losses
+        self.model, self.opt, self.loss_fn = model, optimizer, losses.on_device(loss_fn, x.device)  # (a marker's weights: on the GPU)
         self.x, self.ei, self.ew = x, edge_index, edge_weight
         self.bucket = bucket if bucket is not None else gdist.bucket_for(model)
         self.use_graph = use_graph
@@ -55,6 +56,8 @@ class TrainStep:
         self._loss_sum = torch.zeros((), dtype=torch.float32, device=x.device)
         self._hyper = None              # (betas, eps, weight_decay) baked into the captured optimizer launch
         self._clip = None               # max_grad_norm baked into the capture (None: no clipping launches in it)
+        self._wsig = None               # the loss's weight tensors baked into the capture (their pointers are launch arguments)
+        self.n_captures = 0             # captures so far (a new one: changed hyper-parameters, label form, weight tensor)
         self._one = torch.ones((), device=x.device)
         self._g_fb = self._g_tail = None
         self._split = False
@@ -76,12 +79,22 @@ class TrainStep:
         h = self.opt.hyper() if hasattr(self.opt, "hyper") else None
         return (h, None) if h is None else (tuple(h[:4]), h[4] if len(h) > 4 else None)
 
+    def _weight_sig(self):
+        """What a capture bakes in of a weighted loss (losses.fusable_spec): the weight tensors' addresses are launch
+        arguments — another tensor means a new capture, like a change of betas; the VALUES are read at replay, so an in-place
+        edit needs none."""
+        from . import losses
+        spec = losses.fusable_spec(self.loss_fn)
+        if spec is None:
+            return None
+        return tuple(None if w is None else (w.data_ptr(), w.numel()) for w in spec[1:])
+
     # -- the step body, split at the collective ---------------------------------------------------
     def _fused_head(self):
         """Head + loss fusable: "linear" (a bare nn.Linear head) or "mlp2" (a two-layer models.MLP, losses.fusable_head)
         with a loss glass_amd.losses recognises; else None."""
         from . import losses
-        if losses.fusable_mode(self.loss_fn) is None:
+        if losses.fusable_spec(self.loss_fn) is None:
             return None
         return losses.fusable_head(self.model.preds[0])
 
@@ -121,7 +134,7 @@ class TrainStep:
             emb = self.model.NodeEmb(self.x, self.ei, self.ew, z)
             pooled = self.model.Pool(emb, self._pos, self.model.pools[0])
             head_loss = losses.head_loss if kind == "linear" else losses.mlp_head_loss
-            loss, _logits = head_loss(pooled, self.model.preds[0], self._y, losses.fusable_mode(self.loss_fn),
+            loss, _logits = head_loss(pooled, self.model.preds[0], self._y, losses.fusable_spec(self.loss_fn),
                                       direct=hasattr(self.bucket, "flat_param"))
         else:
             pred = self.model(self.x, self.ei, self.ew, self._pos, z, id=0)
@@ -216,6 +229,7 @@ class TrainStep:
                 self._program_step())
 
     def _capture(self):
+        self.n_captures += 1
         dist_on = gdist.is_distributed()
         self._g_fb = torch.cuda.CUDAGraph()
         # With a process group alive, its watchdog THREAD polls the completion events of earlier collectives with
@@ -397,11 +411,12 @@ class TrainStep:
         self._labels.in_head = True
         sig = self._labels.head_signature()
         hyper, clip = self._opt_hyper()
-        if (first or not self.graphed or (hyper, clip) != (self._hyper, self._clip) or sig != self._head_sig or not was_head or
-                self._recapture):
+        wsig = self._weight_sig()
+        if (first or not self.graphed or (hyper, clip, wsig) != (self._hyper, self._clip, self._wsig) or sig != self._head_sig or
+                not was_head or self._recapture):
             if first:
                 self._warmup()   # (eager steps through the same head launch: they consume the first batches of the cursor)
-            self._hyper, self._clip, self._head_sig, self._recapture = hyper, clip, sig, False
+            self._hyper, self._clip, self._wsig, self._head_sig, self._recapture = hyper, clip, wsig, sig, False
             self._capture()
             self._labels.set_epoch(pos_all, y_all, idx_batches, self._pos, self._y, wrap=wrap)  # cursor back to batch 0
         return True
@@ -432,13 +447,14 @@ class TrainStep:
             self._recapture = self.graphed
         self._load_batch(pos, y, index)
         hyper, clip = self._opt_hyper()
-        if first or (self.graphed and ((hyper, clip) != (self._hyper, self._clip) or self._recapture)):
+        wsig = self._weight_sig()
+        if first or (self.graphed and ((hyper, clip, wsig) != (self._hyper, self._clip, self._wsig) or self._recapture)):
             self._recapture = False
             # (betas / eps / weight_decay / max_grad_norm are launch arguments: a changed param_groups entry means a new
             # capture; the learning rate lives in device memory and needs none)
             if first:
                 self._warmup()
-            self._hyper, self._clip = hyper, clip
+            self._hyper, self._clip, self._wsig = hyper, clip, wsig
             if self.use_graph:
                 self._capture()
         if hasattr(self.opt, "sync_lr"):

@@ -64,6 +64,8 @@ def _epoch_loss(mean_loss, dataloader):
 def train(optimizer, model, dataloader, loss_fn):
     """One epoch; returns the mean per-step loss.  batch = (x, ei, ea, pos, [z,] y)."""
     model.train()
+    from . import losses
+    losses.on_device(loss_fn, next(model.parameters()).device)  # a weighted marker loss keeps its weights beside the model
     step = _graph_step(optimizer, model, dataloader, loss_fn)
     if step is not None:
         # The loader's own iteration would select the batch (`pos[perm], y[perm]`: two index kernels) and label it (z_fn =

@@ -803,6 +803,53 @@ int glass_readout_max_train_f32(const float* jk, int64_t ldj, const float* gn_sa
                                 const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
                                 float* loss_sum, void* stream);           /* impl/models.py:300-303, 346-350 */
 
+/* K8w  class-weighted losses: siblings of the K8 / K8m / K8r training entries that carry `class_weight` (float[K], torch's
+ *      CrossEntropyLoss(weight=)) and `pos_weight` (float[K], one per output column, BCEWithLogitsLoss(pos_weight=)) just
+ *      before `stream`.  Either may be NULL, at most one may be set; every value finite and > 0 (the caller's business).
+ *        cross-entropy  loss = sum_b w[t_b] (lse_b - z_b[t_b]) / sum_b w[t_b];  dlogits[b,k] = gl w[t_b] / sum_w (softmax - [k = t_b]);
+ *                       a target outside [0, K) adds nothing to either sum and has no gradient
+ *        BCE            c = 1 + (p_k - 1) y;  term = (1 - y) z + c (log1p(exp(-|z|)) + max(-z, 0));  d/dz = c sigmoid(z) - p_k y;
+ *                       the mean stays over B*K
+ *      The weight sum is recomputed in fp64, in a fixed order, by every workgroup that needs it (no launch, no float atomic):
+ *      launch counts and workspace sizes are the unweighted entries', results bitwise repeatable.  The pointers are read at
+ *      launch time (a replayed graph follows an in-place change of the values).  With two NULLs an entry launches exactly
+ *      what its unweighted sibling launches — those pass two NULLs to the same code.  Refused before any launch with
+ *      GLASS_E_UNSUPPORTED: both pointers set, class_weight with mode 1, pos_weight with mode 0. */
+int glass_head_loss_fwd_w_f32(const float* pooled, int64_t ldp, const float* W, const float* bias, const void* target,
+                              int mode, int64_t B, int64_t C, int64_t K, float* logits, float* prob, float* loss,
+                              const float* class_weight, const float* pos_weight, void* stream);
+int glass_head_loss_bwd_w_f32(const float* pooled, int64_t ldp, const float* W, const float* prob, const void* target,
+                              int mode, const float* grad_loss, int64_t B, int64_t C, int64_t K, float* dpooled,
+                              int64_t lddp, float* dW, float* db, int accumulate, const float* class_weight,
+                              const float* pos_weight, void* stream);
+int glass_head_mlp_loss_fwd_w_f32(const float* pooled, int64_t ldp, const float* W1, const float* b1, const float* W2,
+                                  const float* b2, const void* target, int mode, int act, float p_drop,
+                                  const uint64_t* rng_state, uint64_t call_id, int64_t B, int64_t C, int64_t Hd, int64_t K,
+                                  float* hidden_pre, float* logits, float* prob, float* loss, const float* class_weight,
+                                  const float* pos_weight, void* stream);
+int glass_head_mlp_loss_bwd_w_f32(const float* pooled, int64_t ldp, const float* W1, const float* W2, const float* hidden_pre,
+                                  const float* prob, const void* target, int mode, int act, float p_drop,
+                                  const uint64_t* rng_state, uint64_t call_id, const float* grad_loss, int64_t B, int64_t C,
+                                  int64_t Hd, int64_t K, float* ws, float* dpooled, int64_t lddp, float* dW1, float* db1,
+                                  float* dW2, float* db2, int accumulate, const float* class_weight,
+                                  const float* pos_weight, void* stream);
+int glass_readout_train_w_f32(const float* jk, int64_t ldj, const float* gn_saved, const float* gamma, const float* alpha,
+                              const int64_t* pos, int64_t B, int64_t Smax, int pool_mode, const float* Wh, const float* bh,
+                              const void* target, int loss_mode, int64_t K, const float* grad_loss, float* pooled,
+                              float* logits, float* loss, float* djk, int64_t lddj, float* dWh, float* dbh, int acc_head,
+                              float* dgamma, float* dbeta, float* dalpha, int acc_gn, void* ws, int64_t n_nodes, int64_t C,
+                              const uint8_t* mask, const int32_t* lab_rows, const int32_t* lab_count,
+                              const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
+                              float* loss_sum, const float* class_weight, const float* pos_weight, void* stream);
+int glass_readout_max_train_w_f32(const float* jk, int64_t ldj, const float* gn_saved, const float* gamma, const float* alpha,
+                                  const int64_t* pos, int64_t B, int64_t Smax, const float* Wh, const float* bh,
+                                  const void* target, int loss_mode, int64_t K, const float* grad_loss, float* pooled,
+                                  float* logits, float* loss, float* djk, int64_t lddj, float* dWh, float* dbh, int acc_head,
+                                  float* dgamma, float* dbeta, float* dalpha, int acc_gn, void* ws, int64_t n_nodes, int64_t C,
+                                  const uint8_t* mask, const int32_t* lab_rows, const int32_t* lab_count,
+                                  const glass_gn_src* gn_src, int64_t* gn_bwd_acc, int gn_bwd_rep, void* scatter_ws,
+                                  float* loss_sum, const float* class_weight, const float* pos_weight, void* stream);
+
 /*     Two small device-to-device copies in one launch (4-byte granularity): a training step that is replayed from a
  *     captured graph reads its batch (pos, target) from fixed buffers; this fills both per step. */
 int glass_copy_pair(void* dst0, const void* src0, int64_t bytes0, void* dst1, const void* src1, int64_t bytes1,
