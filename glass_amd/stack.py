@@ -16,11 +16,15 @@ the layers themselves:
   * with a fusable readout (`step_supported`): final GraphNorm apply + pooling + Linear head + loss and their
     backward are the four launches of K8r, and the labels are scattered straight from `pos`.
 
+Which form each step takes is decided once per pass by `plan_stack` (a pure function of plain values -> `StackPlan`, the
+only reader of the switches below); forward, readout and backward branch on plan fields alone.
+
 Used when every layer takes the fused dense path (ParamArena present, GLASSConv layers of equal width that
 glass_dual_linear_supported() accepts — hidden 64 / 128 —, ELU, GraphNorm on); anything else keeps the per-op path.
 Same kernels, same dropout call ids -> same dropout masks as the per-op path; no float atomics -> bitwise repeatable.
 """
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -28,26 +32,30 @@ import torch
 from . import _lib, ops
 from .ops import ACT_ELU, ACT_NONE, ACT_RELU, _stream
 
-USE_EMBED_TABLE = os.environ.get("GLASS_EMBED_TABLE", "1") != "0"  # A/B switch: lookup + emb_gn through the table
-USE_READOUT = os.environ.get("GLASS_READOUT", "1") != "0"          # A/B switch: fused training readout (K8r)
-
-
-def _check(rc, what):
-    _lib.check(rc, what)
-
-
-USE_GN_EXACT = os.environ.get("GLASS_GN_EXACT", "1") != "0"  # A/B switch: exact GraphNorm accumulators instead of partials + finalize
+# ---- A/B switches, row limits and replica counts: ONE block.  plan_stack() and the gates next to it are their only readers in
+# this file, and read them at call time (the tests set them by name).  Most off-positions are also the shape fallbacks.
+USE_EMBED_TABLE = os.environ.get("GLASS_EMBED_TABLE", "1") != "0"  # lookup + emb_gn through the table
+USE_READOUT = os.environ.get("GLASS_READOUT", "1") != "0"          # fused training readout (K8r)
+USE_GN_EXACT = os.environ.get("GLASS_GN_EXACT", "1") != "0"  # exact GraphNorm accumulators instead of partials + finalize
+USE_GN_EXACT_FWD = os.environ.get("GLASS_GN_EXACT_FWD", "1") != "0"  # ... for the forward sums as well
 USE_READOUT_TWO = os.environ.get("GLASS_READOUT_TWO", "1") != "0"  # readout as two launches (backward sums in exact accumulators)
 USE_GN_BWD_IN_COMB = os.environ.get("GLASS_GN_BWD_IN_COMB", "1") != "0"  # gns[l]'s backward apply inside the comb backward launch
-USE_GN_EXACT_FWD = os.environ.get("GLASS_GN_EXACT_FWD", "1") != "0"  # ... for the forward sums as well
+USE_FUSED_TAIL = os.environ.get("GLASS_FUSED_TAIL", "1") != "0"  # K1 slot sums + table backward + Adam as one launch
+USE_FUSED_BWD = os.environ.get("GLASS_FUSED_BWD", "1") != "0"  # data + weight gradient of a pair as one launch
+USE_GATHER_IN_TRANS = os.environ.get("GLASS_GATHER_IN_TRANS", "1") != "0"  # embedding lookup inside layer 0's trans kernel
+USE_COMB_EFF = os.environ.get("GLASS_COMB_EFF", "1") != "0"  # comb pair through effective per-label weights
 # above this many rows the partials + finalize form is kept: thousands of workgroups adding to the same few replicas would
 # queue at the memory-side atomic units, and a ~5 us finalize launch no longer shows against the kernels around it
 GN_EXACT_MAX_ROWS = 1 << 18
-GN_EXACT_FWD_ONLY_MAX_ROWS = 1 << 14  # the forward sums alone (hidden 128, one layer): see StackProgram.forward
-GN_EXACT_READOUT_MAX_ROWS = 1 << 16  # the readout's backward sums alone (H * L <= 128): see StackProgram.forward
-USE_FUSED_TAIL = os.environ.get("GLASS_FUSED_TAIL", "1") != "0"  # A/B switch: K1 slot sums + table backward + Adam as one launch
-USE_GATHER_IN_TRANS = os.environ.get("GLASS_GATHER_IN_TRANS", "1") != "0"  # A/B switch: embedding lookup inside layer 0's trans kernel
-USE_COMB_EFF = os.environ.get("GLASS_COMB_EFF", "1") != "0"  # A/B switch: comb pair through effective per-label weights
+GN_EXACT_FWD_ONLY_MAX_ROWS = 1 << 14  # the forward sums alone (hidden 128, one layer): see plan_stack
+GN_EXACT_READOUT_MAX_ROWS = 1 << 16  # the readout's backward sums alone (H * L <= 128): see plan_stack
+# replicas of the exact accumulators (gn_acc.h) by producer: the stand-alone statistics kernel's workgroups all finish
+# together (their adds to one replica queue up: 10.6 / 8.1 / 6.6 us with 4 / 8 / 16), the dense kernels' epilogues are spread
+# over the launch — and every consumer workgroup reads n_rep * 2 KB
+REP_STATS, REP_DENSE = 16, int(os.environ.get("GLASS_REP_DENSE", "16"))
+
+
+_check = _lib.check
 
 
 _PROLOGUE_DONE = False
@@ -148,23 +156,143 @@ class BatchLabels:
         self.loaded = True
 
 
-def _comb_eff_ld(emb, H):
+def _eff_ld(H, L, jk):
     """row stride (floats) at which glass_comb_eff_max_rows caps the comb pair's rows: the widest of its operands in this
     program — the JK output slices (H * L wide rows), the [n, 2H] data gradient — and at least 4H, the cap the effective
     path has always been run under"""
-    return max(4 * H, H * len(emb.convs) if emb.jk else H)
+    return max(4 * H, H * L if jk else H)
 
 
-def _comb_eff_ok(conv, labels, H, ld):
-    """forward AND backward of the comb pair in effective-weight form (hidden 64); ld: _comb_eff_ld"""
-    return (USE_COMB_EFF and labels is not None and getattr(conv, "_stack_eff", {}).get("comb", (None, None))[1] is not None and
-            bool(_lib.load().glass_comb_eff_supported(H)) and labels.n <= _lib.load().glass_comb_eff_max_rows(ld))
+def _comb_eff_ld(emb, H):
+    return _eff_ld(H, len(emb.convs), emb.jk)
 
 
-def _comb_eff_fwd_ok(conv, labels, H, ld):
-    """the forward alone (also hidden 128)"""
-    return (USE_COMB_EFF and labels is not None and "comb" in getattr(conv, "_stack_eff", {}) and
-            bool(_lib.load().glass_comb_eff_fwd_supported(H)) and labels.n <= _lib.load().glass_comb_eff_max_rows(ld))
+class LayerPlan(NamedTuple):
+    """Kernel forms of one layer.  *_acc: block of the exact accumulators (gn_acc.h; StackPlan) that takes those sums, -1:
+    float64 partials of *_blocks row blocks (0: no partials) and a finalize step."""
+    comb_fwd: str       # "eff" | "dual" | "eff_nostats" (the unlabeled last layer: nothing normalises its output)
+    gn_fwd_acc: int     # conv.gn's forward sums of a_l (-1: the stand-alone statistics + finalize kernel)
+    c_acc: int          # the forward sums of c_l, from the comb kernel's epilogue
+    c_blocks: int
+    comb_bwd: str       # "eff" | "dual"
+    gn_bwd_acc: int     # conv.gn's backward sums, from the comb data-gradient epilogue
+    gn_bwd_blocks: int
+    gns_bwd_acc: int    # gns[l-1]'s backward sums (l > 0), from the trans data-gradient epilogue (-1: StackPlan.dense_blocks)
+    gn_in_comb: bool    # gns[l]'s backward apply rides in this layer's comb backward launch (glass_gn_bwd_src)
+
+
+class StackPlan(NamedTuple):
+    """Every kernel choice of one forward + backward of the program, taken once (plan_stack) from plain values."""
+    embed: str          # "identity" (unlabeled: gather in trans, no emb_gn) | "gather" (in trans) | "table" (K3n) | "plain" (K3+K4)
+    skip_prologue: bool  # an evaluation forward behind a shared prologue (prologue_done)
+    head: bool          # the prologue launch also labels the batch (glass_step_head_f32)
+    exact: str          # "all" | "fwd_only" | "readout_only" | "none": which sums live in exact accumulators
+    n_bwd: int          # accumulator layout, int64 words: [n_bwd + n_fwd blocks of w_h | w_ro], acc_words in all; the
+    n_fwd: int          # backward blocks come first (LayerPlan.gn_bwd_acc / gns_bwd_acc), then L for conv.gn's forward sums,
+    w_h: int            # then L for the sums of c_l (consecutive: the column blocks of the jumping-knowledge buffer)
+    w_ro: int           # the final GraphNorm's backward sums (readout in two launches), 0: three launches
+    acc_words: int
+    final_src: tuple    # (first block, blocks) of c_l sums the final GraphNorm's coefficients come from; None: finalize launch
+    n_rep: int          # replicas per accumulator the dense kernels' epilogues add to
+    dense_blocks: int   # row blocks of the fused dense kernels' float64 partials
+    fused_bwd: bool     # data + weight gradient of a Linear pair through glass_dual_linear_bwd_f32
+    tail: str           # "unlabeled" | "fused" (product + table backward [+ Adam] in one launch) | "table" | "plain"
+    layers: tuple
+
+
+def plan_stack(H, L, V, n, jk, unlabeled, train, keep, has_labels, labels_cap, in_head, readout, prologue_done, advance, eff):
+    """The StackPlan of one pass.  readout: None, or (pool mode, loss given as a spec tuple) of the fused training readout;
+    eff[l] = (forward image, backward image) of layer l's effective comb weights present (conv._stack_eff).  The ONLY reader
+    of the switches, row limits and support queries in this file besides the gates below; reads them on every call."""
+    lib, has_ro = _lib.load(), readout is not None
+    C_out = H * L if jk else H
+    # comb pair in effective-weight form: forward AND backward at hidden 64, the forward alone also at hidden 128
+    in_rows = USE_COMB_EFF and has_labels and n <= lib.glass_comb_eff_max_rows(_eff_ld(H, L, jk))
+    eff_fwd = [bool(in_rows and f and lib.glass_comb_eff_fwd_supported(H)) for f, _ in eff]
+    eff_bwd = [bool(in_rows and b and lib.glass_comb_eff_supported(H)) for _, b in eff]
+    # exact cross-workgroup GraphNorm sums (gn_acc.h) for the backward column sums: one int64 block per GraphNorm whose
+    # backward sums come from a data-gradient epilogue (conv.gn of every layer, gns[l] between layers), zero-filled by the
+    # prologue launch — their finalize launches disappear
+    # ... and for the forward sums when the fused readout applies the final GraphNorm
+    exact_all = USE_GN_EXACT and bool(lib.glass_gn_exact_supported(H)) and n <= GN_EXACT_MAX_ROWS
+    # the forward sums alone where every kernel that applies such a GraphNorm takes the pending form: the staged comb
+    # forward (conv.gn) and the readout (final GraphNorm) do at hidden 128 too, the tiled trans kernel (gns[l] between
+    # layers) does not — so: one layer, comb pair in effective-weight form
+    # (measured at hidden 128, one layer, with / without: 0.2552 / 0.2564 ms at N = 12 000, 0.3526 / 0.3491 at 20 000,
+    # 0.6272 / 0.6106 at 50 000 — every consumer workgroup folds 64 KB of replicas, which only pays while the launch is
+    # about one workgroup per CU: hence the row limit)
+    fwd_only = (not exact_all and USE_GN_EXACT and n <= GN_EXACT_FWD_ONLY_MAX_ROWS and
+                bool(lib.glass_gn_exact_fwd_supported(H)) and L == 1 and all(eff_fwd))
+    exact, n_bwd, n_fwd, w_h, w_ro = "none", 0, 0, 0, 0
+    if exact_all or fwd_only:
+        n_bwd = 2 * L - 1 if (keep and exact_all) else 0
+        n_fwd = 2 * L if ((has_ro or unlabeled) and USE_GN_EXACT_FWD) else 0
+        if n_bwd + n_fwd:
+            # ... and one block of L*H (jk) / H columns for the final GraphNorm's backward sums, added to by the readout's
+            # first kernel and folded by its backfill launch (two launches instead of three)
+            exact, w_h = ("all" if exact_all else "fwd_only"), int(lib.glass_gn_exact_words(H))
+            w_ro = int(lib.glass_gn_exact_words(C_out)) if (has_ro and keep and USE_READOUT_TWO) else 0
+    elif (USE_GN_EXACT and USE_READOUT_TWO and has_ro and keep and has_labels and H % 4 == 0 and C_out <= 128 and
+          n <= GN_EXACT_READOUT_MAX_ROWS):
+        # the readout's own block alone: its backward column sums in exact accumulators, folded by the backfill launch —
+        # two launches instead of three (every backfill workgroup folds n_rep * 2C sums: narrow outputs, mid-size graphs)
+        exact, w_ro = "readout_only", int(lib.glass_gn_exact_words(C_out))
+    acc_words = (n_bwd + n_fwd) * w_h + w_ro
+    dense_blocks = -(-n // int(lib.glass_dual_linear_stat_rows(H)))  # rows per workgroup of the fused dense kernels
+    layers = []
+    for l in range(L):
+        last = l + 1 == L
+        no_stats = unlabeled and last
+        c_blocks = 0 if (n_fwd or no_stats) else \
+            int(lib.glass_comb_eff_fwd_blocks(n, H, labels_cap)) if eff_fwd[l] else dense_blocks
+        gn_bwd_blocks = 0 if n_bwd else int(lib.glass_comb_eff_blocks(n, H, labels_cap)) if eff_bwd[l] else dense_blocks
+        layers.append(LayerPlan(
+            comb_fwd="eff_nostats" if no_stats else "eff" if eff_fwd[l] else "dual",
+            gn_fwd_acc=n_bwd + l if n_fwd else -1, c_acc=n_bwd + L + l if (n_fwd and not no_stats) else -1, c_blocks=c_blocks,
+            comb_bwd="eff" if eff_bwd[l] else "dual", gn_bwd_acc=2 * l if n_bwd else -1, gn_bwd_blocks=gn_bwd_blocks,
+            gns_bwd_acc=2 * l - 1 if (n_bwd and l) else -1,
+            gn_in_comb=bool(not last and USE_GN_BWD_IN_COMB and n_bwd and eff_bwd[l] and
+                            lib.glass_comb_eff_bwd_gn_src_supported(n, H))))
+    # Hidden 64 with the label bytes already made: layer 0's trans kernel gathers its operand rows from the embedding table
+    # itself and normalises them with emb_gn's table statistics, which ride in the prologue launch next to the weight
+    # packing — no table-apply kernel, no gather launch.  The unlabeled stack gathers under identity coefficients.
+    use_table = unlabeled or (V <= _lib.EMBED_NORM_MAX_ROWS and USE_EMBED_TABLE)
+    if unlabeled:
+        embed = "identity"
+    elif use_table and has_labels and USE_GATHER_IN_TRANS and lib.glass_dual_linear_fwd_gather_supported(H):
+        embed = "gather"
+    else:
+        embed = "table" if use_table else "plain"
+    head = bool(has_labels and in_head and train)
+    return StackPlan(
+        embed=embed, skip_prologue=bool(embed in ("table", "plain") and prologue_done and not advance and not acc_words and not head),
+        head=head, exact=exact, n_bwd=n_bwd, n_fwd=n_fwd, w_h=w_h, w_ro=w_ro, acc_words=acc_words,
+        final_src=None if (not n_fwd or unlabeled) else (n_bwd + L, L) if jk else (n_bwd + 2 * L - 1, 1), n_rep=REP_DENSE,
+        dense_blocks=dense_blocks, fused_bwd=bool(USE_FUSED_BWD),
+        tail="unlabeled" if unlabeled else "plain" if embed == "plain" else "fused" if USE_FUSED_TAIL else "table",
+        layers=tuple(layers))
+
+
+def _plan_for(emb, n, keep, labels, readout, advance):
+    """plan_stack() for this module, batch and call (labels: as resolved by the forward)."""
+    V, H = emb.input_emb.weight.shape
+    images = [getattr(c, "_stack_eff", {}).get("comb") for c in emb.convs]
+    return plan_stack(H, len(emb.convs), V, n, bool(emb.jk), not hasattr(emb, "emb_gn"), emb.training, keep, labels is not None,
+                      labels.cap if labels is not None else 0, bool(getattr(labels, "in_head", False)),
+                      None if readout is None else (readout[1], isinstance(readout[4], tuple)),
+                      _PROLOGUE_DONE, advance, tuple((im is not None, im is not None and im[1] is not None) for im in images))
+
+
+def _unlabeled_forms_ok(H):
+    """what the unlabeled stack cannot run without: exact accumulators and the effective comb pair (gate: supported_unlabeled)"""
+    lib = _lib.load()
+    return bool(USE_GN_EXACT and lib.glass_gn_exact_supported(H) and USE_COMB_EFF and lib.glass_comb_eff_supported(H))
+
+
+def _readout_ok(mode, C, K):
+    """the fused training readout takes this pooling mode and these widths (gate: step_supported)"""
+    lib = _lib.load()
+    return USE_READOUT and bool(lib.glass_readout_max_supported(C, K) if mode == "max" else lib.glass_readout_supported(C, K, _lib.POOL_MODES[mode]))
 
 
 class _PendingStats:
@@ -181,10 +309,9 @@ def _saved_args(saved):
     return saved.data_ptr(), 0
 
 
-# replicas of the exact accumulators (gn_acc.h) by producer: the stand-alone statistics kernel's workgroups all finish
-# together (their adds to one replica queue up: 10.6 / 8.1 / 6.6 us with 4 / 8 / 16), the dense kernels' epilogues are spread
-# over the launch — and every consumer workgroup reads n_rep * 2 KB
-REP_STATS, REP_DENSE = 16, int(os.environ.get("GLASS_REP_DENSE", "16"))
+def _pl(t):
+    """(pointer, row stride) of an optional matrix operand"""
+    return (0, 0) if t is None else (t.data_ptr(), t.stride(0))
 
 
 def _rep(t):
@@ -197,6 +324,19 @@ def _stats_args(stats):
     if stats is None:
         return 0, 0
     return stats.data_ptr(), _rep(stats)
+
+
+def _gn_epilogue_args(gn, dev, p_drop=0.0):
+    """(the nine GraphNorm arguments of a data-gradient epilogue, dropout words pointer).  gn = (partial, x, saved, alpha, act,
+    p, call_id) or None; an int64 `partial` = the exact accumulators of gn_acc.h; the dropout words are passed when that
+    GraphNorm or the kernel's own dropout (p_drop) draws a mask."""
+    if gn is None:
+        gp, gargs = 0.0, (0, 0, 0, 0, 0, 0, 0.0, 0, 0)
+    else:
+        gpart, gx, gsaved, galpha, gact, gp, gcall = gn
+        gargs = (gpart.data_ptr(), gx.data_ptr(), gx.stride(0), gsaved.data_ptr(), galpha.data_ptr(), gact, float(gp), gcall,
+                 _rep(gpart))
+    return gargs, (ops.rng_tensor(dev).data_ptr() if (p_drop > 0 or gp > 0) else 0)
 
 
 def _comb_eff_fwd(xa, xb, conv, mask, out, stats, gn, labels):
@@ -216,16 +356,13 @@ def _comb_eff_bwd(dsrc, conv, mask, out, xa, xb, pending, acc, gn, labels, dsrc_
     """dsrc_gn (a _lib.GnBwdSrc): dsrc is not materialised — the kernels derive it on load from the gradient of the
     GraphNorm behind this layer (glass_gn_bwd_src); dsrc is then only a shape carrier (the tensor dy)."""
     n, H = dsrc.shape
-    gpart, gx, gsaved, galpha, gact, gp, gcall = gn
-    rng = ops.rng_tensor(dsrc.device).data_ptr() if (gp > 0 or (dsrc_gn is not None and dsrc_gn.p_drop > 0)) else 0
+    g, rng = _gn_epilogue_args(gn, dsrc.device, 0.0 if dsrc_gn is None else dsrc_gn.p_drop)
     stack = conv._stack["comb"]
     ws = ops._wgrad_workspace(dsrc.device, n, 2 * H, 2 * H, slot=("stack", len(pending)),
                               min_bytes=int(_lib.load().glass_comb_eff_ws_bytes(n, H, labels.cap)))
     rc = _lib.load().glass_comb_eff_bwd_f32(0 if dsrc_gn is not None else dsrc.data_ptr(), dsrc.stride(0), mask.data_ptr(), float(conv.z_ratio),
                                             conv._stack_eff["comb"][1].data_ptr(), out.data_ptr(), out.stride(0), n, H,
-                                            gpart.data_ptr(), gx.data_ptr(), gx.stride(0), gsaved.data_ptr(),
-                                            galpha.data_ptr(), ops.act_word(gact), float(gp), rng, gcall, _rep(gpart),
-                                            xa.data_ptr(), xa.stride(0),
+                                            *g[:5], ops.act_word(g[5]), g[6], rng, g[7], g[8], xa.data_ptr(), xa.stride(0),
                                             xb.data_ptr(), xb.stride(0), ws.data_ptr(), labels.rows.data_ptr(),
                                             labels.count.data_ptr(), labels.cap, 0 if dsrc_gn is None else dsrc_gn.ptr, _stream())
     _check(rc, "glass_comb_eff_bwd_f32")
@@ -290,34 +427,18 @@ class _GN:
                                                    saved.data_ptr(), act, float(p_drop), rng, call_id, _stream())
         _check(rc, "glass_graphnorm_apply_f32")
 
-    def bwd_from_stats(self, dy, x, saved, dx, partial, act, p_drop, call_id, addend=None, acc=1):
-        """Backward with the two column sums already accumulated (data-gradient epilogue): finalize + apply."""
+    def bwd(self, dy, x, saved, dx, act, p_drop, call_id, addend=None, acc=1, partial=None):
+        """partial: the two column sums are already accumulated (a data-gradient epilogue wrote them: float64 partials, or
+        exact accumulators) — finalize + apply instead of the full backward."""
         m = self.mod
         n, C = x.shape
-        ws = ops._graphnorm_ws(x.device, n, C)
         rng = ops.rng_tensor(x.device).data_ptr() if p_drop > 0 else 0
-        ap, lda = (0, 0) if addend is None else (addend.data_ptr(), addend.stride(0))
-        rc = _lib.load().glass_graphnorm_bwd_from_stats_f32(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0),
-                                                            dx.data_ptr(), dx.stride(0), ap, lda, n, C,
-                                                            m.weight.data_ptr(), m.mean_scale.data_ptr(), saved.data_ptr(),
-                                                            partial.data_ptr(), -_rep(partial) if partial.dtype == torch.int64 else partial.shape[0],
-                                                            m.weight.grad.data_ptr(), m.bias.grad.data_ptr(),
-                                                            m.mean_scale.grad.data_ptr(), acc, act, float(p_drop), rng,
-                                                            call_id, ws.data_ptr(), _stream())
-        _check(rc, "glass_graphnorm_bwd_from_stats_f32")
-
-    def bwd(self, dy, x, saved, dx, act, p_drop, call_id, addend=None, acc=1):
-        m = self.mod
-        n, C = x.shape
-        ws = ops._graphnorm_ws(x.device, n, C)
-        rng = ops.rng_tensor(x.device).data_ptr() if p_drop > 0 else 0
-        ap, lda = (0, 0) if addend is None else (addend.data_ptr(), addend.stride(0))
-        rc = _lib.load().glass_graphnorm_bwd_f32(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), dx.data_ptr(),
-                                                 dx.stride(0), ap, lda, n, C, m.weight.data_ptr(),
-                                                 m.mean_scale.data_ptr(), saved.data_ptr(), m.weight.grad.data_ptr(),
-                                                 m.bias.grad.data_ptr(), m.mean_scale.grad.data_ptr(), acc, act,
-                                                 float(p_drop), rng, call_id, ws.data_ptr(), _stream())
-        _check(rc, "glass_graphnorm_bwd_f32")
+        lib, name = _lib.load(), "glass_graphnorm_bwd_f32" if partial is None else "glass_graphnorm_bwd_from_stats_f32"
+        sums = () if partial is None else (partial.data_ptr(), -_rep(partial) if partial.dtype == torch.int64 else partial.shape[0])
+        _check(getattr(lib, name)(*_pl(dy), *_pl(x), *_pl(dx), *_pl(addend), n, C, m.weight.data_ptr(), m.mean_scale.data_ptr(),
+                                  saved.data_ptr(), *sums, m.weight.grad.data_ptr(), m.bias.grad.data_ptr(),
+                                  m.mean_scale.grad.data_ptr(), acc, act, float(p_drop), rng, call_id,
+                                  ops._graphnorm_ws(x.device, n, C).data_ptr(), _stream()), name)
 
 
 def _dual_fwd(xa, xb, stack, mask, z_ratio, act, T, out, stats=None, gn=None, xa_index=None):
@@ -334,12 +455,9 @@ def _dual_fwd(xa, xb, stack, mask, z_ratio, act, T, out, stats=None, gn=None, xa
     else:
         gargs = (0, 0, 0, 0.0, 0, 0, 0, 0)
     iargs = (0, 0) if xa_index is None else (xa_index.data_ptr(), xa.shape[0])
-    rc = _lib.load().glass_dual_linear_fwd_f32(xa.data_ptr(), xa.stride(0), 0 if xb is None else xb.data_ptr(),
-                                               0 if xb is None else xb.stride(0), stack[4].data_ptr(),
-                                               stack[1].data_ptr(), mask.data_ptr(), float(z_ratio), ops.act_word(act),
-                                               0 if T is None else T.data_ptr(), 0 if T is None else T.stride(0),
-                                               out.data_ptr(), out.stride(0), n, H, *_stats_args(stats), *gargs, *iargs,
-                                               _stream())
+    rc = _lib.load().glass_dual_linear_fwd_f32(*_pl(xa), *_pl(xb), stack[4].data_ptr(), stack[1].data_ptr(), mask.data_ptr(),
+                                               float(z_ratio), ops.act_word(act), *_pl(T), *_pl(out), n, H,
+                                               *_stats_args(stats), *gargs, *iargs, _stream())
     _check(rc, "glass_dual_linear_fwd_f32")
 
 
@@ -349,49 +467,29 @@ def _dual_dgrad(dsrc, T, stack, mask, z_ratio, act, n_out, addend, out, drop=Non
     output; its backward column sums are accumulated into `partial` [ceil(n/64), 2, H] float64 by the epilogue."""
     n, H = dsrc.shape
     p_drop, call_id = drop if drop is not None else (0.0, 0)
-    if gn is not None:
-        gpart, gx, gsaved, galpha, gact, gp, gcall = gn
-        gargs = (gpart.data_ptr(), gx.data_ptr(), gx.stride(0), gsaved.data_ptr(), galpha.data_ptr(), gact, float(gp), gcall,
-                 _rep(gpart))  # int64 buffer = the exact accumulators of gn_acc.h
-    else:
-        gp, gargs = 0.0, (0, 0, 0, 0, 0, 0, 0.0, 0, 0)
-    rng = ops.rng_tensor(dsrc.device).data_ptr() if (p_drop > 0 or gp > 0) else 0
-    rc = _lib.load().glass_dual_linear_dgrad_f32(dsrc.data_ptr(), dsrc.stride(0), 0 if T is None else T.data_ptr(),
-                                                 0 if T is None else T.stride(0), mask.data_ptr(), float(z_ratio), ops.act_word(act),
-                                                 stack[5].data_ptr(), n_out, 0 if addend is None else addend.data_ptr(),
-                                                 0 if addend is None else addend.stride(0), float(p_drop), rng, call_id,
-                                                 out.data_ptr(), out.stride(0), n, H, *gargs, _stream())
+    gargs, rng = _gn_epilogue_args(gn, dsrc.device, p_drop)
+    rc = _lib.load().glass_dual_linear_dgrad_f32(*_pl(dsrc), *_pl(T), mask.data_ptr(), float(z_ratio), ops.act_word(act),
+                                                 stack[5].data_ptr(), n_out, *_pl(addend), float(p_drop), rng, call_id,
+                                                 *_pl(out), n, H, *gargs, _stream())
     _check(rc, "glass_dual_linear_dgrad_f32")
 
 
-USE_FUSED_BWD = os.environ.get("GLASS_FUSED_BWD", "1") != "0"  # A/B switch: data + weight gradient of a pair as one launch
-
-
-def _dual_bwd(dsrc, T, stack, mask, z_ratio, act, n_out, addend, out, xa, xb, pending, acc, drop=None, gn=None):
-    """Backward of one Linear pair: _dual_dgrad + _dual_wgrad through glass_dual_linear_bwd_f32 (ONE launch at hidden 64 on
-    small graphs, where the two are independent latency-bound kernels; two launches inside the library otherwise)."""
-    if not USE_FUSED_BWD:
+def _dual_bwd(fused, dsrc, T, stack, mask, z_ratio, act, n_out, addend, out, xa, xb, pending, acc, drop=None, gn=None):
+    """Backward of one Linear pair.  fused (StackPlan.fused_bwd): _dual_dgrad + _dual_wgrad through glass_dual_linear_bwd_f32
+    (ONE launch at hidden 64 on small graphs, where the two are independent latency-bound kernels; two launches inside the
+    library otherwise)."""
+    if not fused:
         _dual_dgrad(dsrc, T, stack, mask, z_ratio, act, n_out, addend, out, drop, gn)
         _dual_wgrad(dsrc, T, stack, mask, z_ratio, act, xa, xb, pending, acc)
         return
     n, H = dsrc.shape
     I = H if xb is None else 2 * H
     p_drop, call_id = drop if drop is not None else (0.0, 0)
-    if gn is not None:
-        gpart, gx, gsaved, galpha, gact, gp, gcall = gn
-        gargs = (gpart.data_ptr(), gx.data_ptr(), gx.stride(0), gsaved.data_ptr(), galpha.data_ptr(), gact, float(gp), gcall,
-                 _rep(gpart))
-    else:
-        gp, gargs = 0.0, (0, 0, 0, 0, 0, 0, 0.0, 0, 0)
-    rng = ops.rng_tensor(dsrc.device).data_ptr() if (p_drop > 0 or gp > 0) else 0
+    gargs, rng = _gn_epilogue_args(gn, dsrc.device, p_drop)
     ws = ops._wgrad_workspace(dsrc.device, n, 2 * H, I, slot=("stack", len(pending)))
-    rc = _lib.load().glass_dual_linear_bwd_f32(dsrc.data_ptr(), dsrc.stride(0), 0 if T is None else T.data_ptr(),
-                                               0 if T is None else T.stride(0), mask.data_ptr(), float(z_ratio), ops.act_word(act),
-                                               stack[5].data_ptr(), n_out, 0 if addend is None else addend.data_ptr(),
-                                               0 if addend is None else addend.stride(0), float(p_drop), rng, call_id,
-                                               out.data_ptr(), out.stride(0), n, H, *gargs, xa.data_ptr(), xa.stride(0),
-                                               0 if xb is None else xb.data_ptr(), 0 if xb is None else xb.stride(0),
-                                               ws.data_ptr(), _stream())
+    rc = _lib.load().glass_dual_linear_bwd_f32(*_pl(dsrc), *_pl(T), mask.data_ptr(), float(z_ratio), ops.act_word(act),
+                                               stack[5].data_ptr(), n_out, *_pl(addend), float(p_drop), rng, call_id,
+                                               *_pl(out), n, H, *gargs, *_pl(xa), *_pl(xb), ws.data_ptr(), _stream())
     _check(rc, "glass_dual_linear_bwd_f32")
     pending.append((ws.data_ptr(), n, 2 * H, I, stack[2].data_ptr(), stack[2].stride(0), stack[3].data_ptr(), acc))
 
@@ -407,11 +505,8 @@ def _dual_wgrad(dout, T, stack, mask, z_ratio, act, xa, xb, pending, acc=1):
     n, H = dout.shape
     I = H if xb is None else 2 * H
     ws = ops._wgrad_workspace(dout.device, n, 2 * H, I, slot=("stack", len(pending)))
-    rc = _lib.load().glass_dual_linear_wgrad_f32(dout.data_ptr(), dout.stride(0), 0 if T is None else T.data_ptr(),
-                                                 0 if T is None else T.stride(0), mask.data_ptr(), float(z_ratio), ops.act_word(act),
-                                                 xa.data_ptr(), xa.stride(0), 0 if xb is None else xb.data_ptr(),
-                                                 0 if xb is None else xb.stride(0), n, H, 0, 0, 0, 1, ws.data_ptr(),
-                                                 _stream())
+    rc = _lib.load().glass_dual_linear_wgrad_f32(*_pl(dout), *_pl(T), mask.data_ptr(), float(z_ratio), ops.act_word(act),
+                                                 *_pl(xa), *_pl(xb), n, H, 0, 0, 0, 1, ws.data_ptr(), _stream())
     _check(rc, "glass_dual_linear_wgrad_f32")
     pending.append((ws.data_ptr(), n, 2 * H, I, stack[2].data_ptr(), stack[2].stride(0), stack[3].data_ptr(), acc))
 
@@ -424,23 +519,24 @@ def _reduce_pending(pending, product=None):
         return _reduce_pending_with_product(pending, *product)
     if not pending:
         return
-    cols = list(zip(*[p if len(p) == 9 else p + (0, ) for p in pending]))
-    u64 = lambda v: np.array(v, dtype=np.uint64)
-    i64 = lambda v: np.array(v, dtype=np.int64)
-    ws, N, O, I, dW, ld, db = u64(cols[0]), i64(cols[1]), i64(cols[2]), i64(cols[3]), u64(cols[4]), i64(cols[5]), u64(cols[6])
-    acc, cap = np.array(cols[7], dtype=np.int32), i64(cols[8])
+    ws, N, O, I, dW, ld, db, acc, cap = _pending_columns(pending)
     rc = _lib.load().glass_linear_wgrad_reduce_batch_f32(len(pending), ws.ctypes.data, N.ctypes.data, O.ctypes.data,
                                                          I.ctypes.data, dW.ctypes.data, ld.ctypes.data, db.ctypes.data,
                                                          acc.ctypes.data, cap.ctypes.data, _stream())
     _check(rc, "glass_linear_wgrad_reduce_batch_f32")
 
 
-def _reduce_pending_with_product(pending, sel, x):
+def _pending_columns(pending):
+    """the pending list as the nine argument arrays of the reduce entries"""
     cols = list(zip(*[p if len(p) == 9 else p + (0, ) for p in pending])) if pending else [()] * 9
     u64 = lambda v: np.array(v, dtype=np.uint64)
     i64 = lambda v: np.array(v, dtype=np.int64)
-    ws, N, O, I, dW, ld, db = u64(cols[0]), i64(cols[1]), i64(cols[2]), i64(cols[3]), u64(cols[4]), i64(cols[5]), u64(cols[6])
-    acc, cap = np.array(cols[7], dtype=np.int32), i64(cols[8])
+    return (u64(cols[0]), i64(cols[1]), i64(cols[2]), i64(cols[3]), u64(cols[4]), i64(cols[5]), u64(cols[6]),
+            np.array(cols[7], dtype=np.int32), i64(cols[8]))
+
+
+def _reduce_pending_with_product(pending, sel, x):
+    ws, N, O, I, dW, ld, db, acc, cap = _pending_columns(pending)
     op = sel.op
     H = x.shape[1]
     G = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
@@ -472,9 +568,7 @@ class StackProgram:
             return False
         code = _act_code(emb.activation)
         H = emb.input_emb.weight.shape[1]
-        lib = _lib.load()
-        if code not in (ACT_ELU, ACT_RELU) or H != 64 or not (USE_GN_EXACT and lib.glass_gn_exact_supported(H) and USE_COMB_EFF and
-                                                            lib.glass_comb_eff_supported(H)):
+        if code not in (ACT_ELU, ACT_RELU) or H != 64 or not _unlabeled_forms_ok(H):
             return False
         for c in emb.convs:
             st = getattr(c, "_stack", {})
@@ -521,29 +615,24 @@ class StackProgram:
             return self._forward(x_flat, z, edge_index, edge_weight, keep, readout, acc, labels, snapshot_rng)
 
     def _forward(self, x_flat, z, edge_index, edge_weight, keep, readout, acc, labels, snapshot_rng):
-        from .models import buildAdj
+        from .models import buildAdj, _act_code
         emb, lib = self.emb, _lib.load()
-        dev = x_flat.device
-        n = x_flat.shape[0]
+        dev, n = x_flat.device, x_flat.shape[0]
         W = emb.input_emb.weight
         V, H = W.shape
-        L = len(emb.convs)
-        train = emb.training
+        L, train = len(emb.convs), emb.training
         p = float(emb.dropout) if train else 0.0
         f32 = dict(dtype=torch.float32, device=dev)
-        # once-per-step prologue, one launch: operand images of the current weights + new dropout masks
-        advance = train and (p > 0 or any(c.dropout > 0 for c in emb.convs))
-        from .models import _act_code
+        advance = train and (p > 0 or any(c.dropout > 0 for c in emb.convs))  # the prologue draws new dropout masks
         act = _act_code(emb.activation)  # ELU or ReLU, the same code in every layer (supported())
+        unl = not hasattr(emb, "emb_gn")  # the unlabeled pre-training stack (models.EmbGConv): see supported_unlabeled
         st = {"n": n, "H": H, "L": L, "p": p, "x_flat": x_flat, "acc": int(acc), "rng_epoch": ops.rng_epoch(dev), "act": act,
-              "stat_rows": int(lib.glass_dual_linear_stat_rows(H))}  # rows per workgroup of the fused dense kernels
+              "unlabeled": unl}
         # labels: z (int64 [N], > 0 = labeled), None (all labeled), or ("pos", pos): labeled = the nodes listed in the
         # padded subgraph matrix — utils.MaxZOZ without materialising z (a byte memset + scatter inside the gather)
         # labels (BatchLabels, already loaded for this batch): the label bytes are an input and the unique labeled rows are
         # listed — the comb pairs then run in effective-weight form at hidden 64.  With ("pos", pos) and no labels handed
         # in, they are computed here (one extra launch; the replayed training step hands them in).
-        unl = not hasattr(emb, "emb_gn")  # the unlabeled pre-training stack (models.EmbGConv): see supported_unlabeled
-        st["unlabeled"] = unl
         if unl:
             labels = emb.__dict__.get("_glass_no_labels")
             if labels is None or labels.n != n or labels.mask.device != dev:
@@ -553,89 +642,44 @@ class StackProgram:
             labels = BatchLabels(n, z[1].numel(), dev)
             labels.load(z[1])
         if labels is not None:
-            zp, pp, npos = 0, 0, -1
-            mask = labels.mask
-        elif isinstance(z, tuple):
-            zp, pp, npos = 0, z[1].data_ptr(), z[1].numel()
-            mask = torch.empty(n, dtype=torch.uint8, device=dev)
+            (zp, pp, npos), mask = (0, 0, -1), labels.mask
         else:
-            zp, pp, npos = (0 if z is None else z.data_ptr()), 0, 0
             mask = torch.empty(n, dtype=torch.uint8, device=dev)
-        st["labels"] = labels
+            zp, pp, npos = (0, z[1].data_ptr(), z[1].numel()) if isinstance(z, tuple) else (0 if z is None else z.data_ptr(), 0, 0)
+        plan = st["plan"] = _plan_for(emb, n, keep, labels, readout, advance)  # every kernel choice below, and the backward's
+        st["labels"], st["mask"] = labels, mask
         h = torch.empty((n, H), **f32)
-        st["mask"] = mask
         gn0 = None if unl else emb.emb_gn
-        use_table = (V <= _lib.EMBED_NORM_MAX_ROWS and USE_EMBED_TABLE) or unl
-        # Hidden 64 with the label bytes already made (labels): layer 0's trans kernel gathers its operand rows from the
-        # embedding table itself (xa_index) and normalises them with emb_gn's table statistics, which ride in the prologue
-        # launch next to the weight packing — no table-apply kernel, no gather launch.
-        first_gn = None
-        # exact cross-workgroup GraphNorm sums (gn_acc.h) for the backward column sums: one int64 block per GraphNorm whose
-        # backward sums come from a data-gradient epilogue (conv.gn of every layer, gns[l] between layers), zero-filled by the
-        # prologue launch — their finalize launches disappear
-        # ... and for the forward sums when the fused readout applies the final GraphNorm: [L] blocks for conv.gn's sums of a_l,
-        # then [L] for the sums of c_l (consecutive: the column blocks of the jumping-knowledge buffer)
-        acc_all = acc_bwd = acc_fwd = acc_ro = None
-        exact_all = USE_GN_EXACT and bool(lib.glass_gn_exact_supported(H)) and n <= GN_EXACT_MAX_ROWS
-        # the forward sums alone where every kernel that applies such a GraphNorm takes the pending form: the staged comb
-        # forward (conv.gn) and the readout (final GraphNorm) do at hidden 128 too, the tiled trans kernel (gns[l] between
-        # layers) does not — so: one layer, comb pair in effective-weight form
-        # (measured at hidden 128, one layer, with / without: 0.2552 / 0.2564 ms at N = 12 000, 0.3526 / 0.3491 at 20 000,
-        # 0.6272 / 0.6106 at 50 000 — every consumer workgroup folds 64 KB of replicas, which only pays while the launch is
-        # about one workgroup per CU: hence the row limit)
-        exact_fwd_only = (not exact_all and USE_GN_EXACT and n <= GN_EXACT_FWD_ONLY_MAX_ROWS and
-                          bool(lib.glass_gn_exact_fwd_supported(H)) and L == 1 and
-                          all(_comb_eff_fwd_ok(conv, labels, H, _comb_eff_ld(emb, H)) for conv in emb.convs))
-        if exact_all or exact_fwd_only:
-            n_bwd = 2 * L - 1 if (keep and exact_all) else 0
-            n_fwd = 2 * L if ((readout is not None or unl) and USE_GN_EXACT_FWD) else 0
-            # ... and one block of L*H (jk) / H columns for the final GraphNorm's backward sums, added to by the readout's
-            # first kernel and folded by its backfill launch (two launches instead of three)
-            w_h = int(lib.glass_gn_exact_words(H))
-            w_ro = int(lib.glass_gn_exact_words(H * L if emb.jk else H)) if (readout is not None and keep and USE_READOUT_TWO) else 0
-            if n_bwd + n_fwd:
-                acc_all = torch.empty((n_bwd + n_fwd) * w_h + w_ro, dtype=torch.int64, device=dev)
-                blocks = acc_all[:(n_bwd + n_fwd) * w_h].view(n_bwd + n_fwd, w_h)
-                acc_bwd = blocks[:n_bwd] if n_bwd else None
-                acc_fwd = blocks[n_bwd:] if n_fwd else None
-                acc_ro = acc_all[(n_bwd + n_fwd) * w_h:] if w_ro else None
-        elif (USE_GN_EXACT and USE_READOUT_TWO and readout is not None and keep and labels is not None and H % 4 == 0 and
-              (H * L if emb.jk else H) <= 128 and n <= GN_EXACT_READOUT_MAX_ROWS):
-            # the readout's own block alone: its backward column sums in exact accumulators, folded by the backfill launch —
-            # two launches instead of three (every backfill workgroup folds n_rep * 2C sums: narrow outputs, mid-size graphs)
-            acc_all = acc_ro = torch.empty(int(lib.glass_gn_exact_words(H * L if emb.jk else H)), dtype=torch.int64, device=dev)
-        st["gn_exact"] = acc_bwd
-        st["gn_exact_readout"] = acc_ro
-        # the step's head launch labels the batch itself (TrainStep.begin_epoch: prologue || labels, glass_step_head_f32)
-        head = labels if (labels is not None and getattr(labels, "in_head", False) and train) else None
-        if unl:
-            # no GraphNorm behind the embedding (impl/models.py:461-463): layer 0's trans kernel gathers the table rows under
-            # identity coefficients (mean 0, rstd 1, scale 1, shift 0) and applies the embedding's dropout (call id 1)
+        # the exact accumulators (StackPlan: backward blocks, forward blocks, the readout's block), zero-filled by the prologue
+        acc_all = torch.empty(plan.acc_words, dtype=torch.int64, device=dev) if plan.acc_words else None
+        blocks = acc_all[:plan.acc_words - plan.w_ro].view(-1, plan.w_h) if plan.n_bwd + plan.n_fwd else None
+        st["acc_blocks"] = blocks
+        st["gn_exact"] = blocks[:plan.n_bwd] if plan.n_bwd else None
+        st["gn_exact_readout"] = acc_all[plan.acc_words - plan.w_ro:] if plan.w_ro else None
+        acc_block = lambda i: None if i < 0 else blocks[i]
+        # once-per-step prologue, one launch: operand images of the current weights + new dropout masks (+ the accumulators'
+        # zero-fill, emb_gn's table statistics, the batch's labels: TrainStep.begin_epoch, glass_step_head_f32)
+        first_gn = table = None
+        if plan.embed in ("identity", "gather"):
             sel = emb._selection(x_flat)
-            ident = emb.__dict__.get("_glass_ident_saved")
-            if ident is None or ident.device != dev:
-                ident = emb.__dict__["_glass_ident_saved"] = torch.cat([torch.zeros(H, **f32), torch.ones(2 * H, **f32), torch.zeros(H, **f32)])
-            emb._glass_arena.refresh_transposes(ops.rng_state(dev) if advance else None, zero=acc_all, head=head)
-            st["emb_table"], st["emb_saved"] = sel, ident
-            first_gn = (ident, ACT_NONE, p, 1)
-        elif use_table and labels is not None and USE_GATHER_IN_TRANS and lib.glass_dual_linear_fwd_gather_supported(H):
-            sel = emb._selection(x_flat)
-            saved = torch.empty(4 * H, **f32)
-            emb._glass_arena.refresh_transposes(ops.rng_state(dev) if advance else None,
-                                                table=(W, V, sel.op.rowptr, gn0, saved, None), zero=acc_all, head=head)
+            if unl:
+                # no GraphNorm behind the embedding (impl/models.py:461-463): layer 0's trans kernel gathers the table rows under
+                # identity coefficients (mean 0, rstd 1, scale 1, shift 0) and applies the embedding's dropout (call id 1)
+                saved = emb.__dict__.get("_glass_ident_saved")
+                if saved is None or saved.device != dev:
+                    saved = emb.__dict__["_glass_ident_saved"] = torch.cat([torch.zeros(H, **f32), torch.ones(2 * H, **f32), torch.zeros(H, **f32)])
+            else:
+                saved = torch.empty(4 * H, **f32)
+                table = (W, V, sel.op.rowptr, gn0, saved, None)
             st["emb_table"], st["emb_saved"] = sel, saved
             first_gn = (saved, ACT_NONE, p, 1)
-        elif _PROLOGUE_DONE and not advance and acc_all is None and head is None:
-            pass  # (evaluation branch behind a shared prologue: prologue_done)
-        else:
-            # once-per-step prologue, one launch: operand images of the current weights + new dropout masks
-            emb._glass_arena.refresh_transposes(ops.rng_state(dev) if advance else None, zero=acc_all, head=head)
+        if not plan.skip_prologue:
+            emb._glass_arena.refresh_transposes(ops.rng_state(dev) if advance else None, table=table, zero=acc_all,
+                                                head=labels if plan.head else None)
         st["rng_epoch"] = ops.rng_epoch(dev)  # (the prologue launch above advanced the dropout stream)
         st["rng_words"] = ops.rng_snapshot(dev) if (snapshot_rng and advance and keep) else None
         ops._rng_cur[ops._dev(dev)] = st["rng_words"]  # the rest of this forward (inside forward()'s rng_scope) reads the snapshot
-        if first_gn is not None:
-            pass
-        elif use_table:
+        if plan.embed == "table":
             # K3n: lookup + emb_gn + dropout through the V-row table (statistics are count-weighted sums over W)
             sel = emb._selection(x_flat)
             saved = torch.empty(4 * H, **f32)
@@ -647,7 +691,7 @@ class StackProgram:
                                                 zp, pp, npos, p, rng, 1, h.data_ptr(), H,
                                                 mask.data_ptr(), n, H, _stream()), "glass_embed_norm_fwd_f32")
             st["emb_table"], st["emb_saved"] = sel, saved
-        else:
+        elif plan.embed == "plain":
             # K3+K4: embedding gather + label byte, then the whole-graph GraphNorm
             h0 = torch.empty((n, H), **f32)
             _check(lib.glass_embed_label_f32(x_flat.data_ptr(), W.data_ptr(), V, zp, pp, npos, h0.data_ptr(), H,
@@ -660,7 +704,7 @@ class StackProgram:
         layers, cstats = [], []
         pending_gn = None  # (saved, act, p, call_id) of the GraphNorm between the previous layer and this one
         c_prev = None
-        for l, conv in enumerate(emb.convs):
+        for l, (conv, lp) in enumerate(zip(emb.convs, plan.layers)):
             if conv.adj is None:
                 conv.adj = buildAdj(edge_index, edge_weight, n, conv.aggr)
             pc = float(conv.dropout) if train else 0.0
@@ -676,29 +720,24 @@ class StackProgram:
                 h = torch.empty((n, H), **f32)
                 _dual_fwd(c_prev, None, conv._stack["trans"], mask, conv.z_ratio, act, T, m, gn=(*pending_gn, h))
             a = conv.adj.fwd.spmm(m)
-            # conv.gn: statistics + finalize here, the apply (+dropout) rides in the comb kernel's operand load
+            # conv.gn: statistics (+ finalize) here, the apply (+dropout) rides in the comb kernel's operand load
             g = torch.empty((n, H), **f32)
-            gsaved = _GN(conv.gn).stats(a) if acc_fwd is None else _GN(conv.gn).stats_exact(a, acc_fwd[l])
+            gsaved = _GN(conv.gn).stats(a) if lp.gn_fwd_acc < 0 else _GN(conv.gn).stats_exact(a, blocks[lp.gn_fwd_acc])
             last = l + 1 == L
             c = jk[:, l * H:(l + 1) * H] if emb.jk else (jk if last else torch.empty((n, H), **f32))
-            # the comb kernel's epilogue also leaves the column statistics of c for the GraphNorm(s) that read it
-            if unl and last:
-                cstat = None  # (nothing normalises the last layer's output: impl/models.py:469)
-                _comb_eff_fwd(a, h, conv, mask, c, None, (gsaved, ACT_NONE, pc, conv.call_base, g), labels)
-            elif _comb_eff_fwd_ok(conv, labels, H, _comb_eff_ld(emb, H)):
-                cstat = acc_fwd[L + l] if acc_fwd is not None else \
-                    torch.empty((int(lib.glass_comb_eff_fwd_blocks(n, H, labels.cap)), 2, H), dtype=torch.float64, device=dev)
-                _comb_eff_fwd(a, h, conv, mask, c, cstat, (gsaved, ACT_NONE, pc, conv.call_base, g), labels)
-            else:
-                cstat = acc_fwd[L + l] if acc_fwd is not None else \
-                    torch.empty((-(-n // st["stat_rows"]), 2, H), dtype=torch.float64, device=dev)
+            # the comb kernel's epilogue also leaves the column statistics of c for the GraphNorm(s) that read it (none at
+            # "eff_nostats": nothing normalises the unlabeled stack's last output, impl/models.py:469)
+            cstat = acc_block(lp.c_acc) if not lp.c_blocks else torch.empty((lp.c_blocks, 2, H), dtype=torch.float64, device=dev)
+            if lp.comb_fwd == "dual":
                 _dual_fwd(a, h, conv._stack["comb"], mask, conv.z_ratio, ACT_NONE, None, c, cstat,
                           gn=(gsaved, ACT_NONE, pc, conv.call_base, g))
+            else:
+                _comb_eff_fwd(a, h, conv, mask, c, cstat, (gsaved, ACT_NONE, pc, conv.call_base, g), labels)
             cstats.append(cstat)
             rec = {"h": h, "T": T, "a": a, "g": g, "gsaved": getattr(gsaved, "saved", gsaved), "c": c, "pc": pc}
             if not last:
-                if acc_fwd is not None:   # the next layer's trans kernel derives gns[l]'s coefficients from the sums of c_l
-                    nsaved = _PendingStats(torch.empty(4 * H, **f32), cstat, 1, emb.gns[l], REP_DENSE)
+                if lp.c_acc >= 0:   # the next layer's trans kernel derives gns[l]'s coefficients from the sums of c_l
+                    nsaved = _PendingStats(torch.empty(4 * H, **f32), cstat, 1, emb.gns[l], plan.n_rep)
                 else:
                     nsaved = _GN(emb.gns[l]).finalize([cstat], n)
                 rec["nsaved"] = getattr(nsaved, "saved", nsaved)
@@ -708,9 +747,9 @@ class StackProgram:
         if unl:
             return jk, (st if keep else None)  # the raw output of the last layer (no final GraphNorm, no JK)
         gnf = _GN(emb.gns[-1])
-        if acc_fwd is not None:  # the readout's first kernel derives the final GraphNorm's coefficients
-            st["final_saved"] = _PendingStats(torch.empty(4 * C_out, **f32), acc_fwd[L:] if emb.jk else acc_fwd[2 * L - 1],
-                                              L if emb.jk else 1, emb.gns[-1], REP_DENSE)
+        if plan.final_src is not None:  # the readout's first kernel derives the final GraphNorm's coefficients
+            first, count = plan.final_src
+            st["final_saved"] = _PendingStats(torch.empty(4 * C_out, **f32), blocks[first:], count, emb.gns[-1], plan.n_rep)
         else:
             st["final_saved"] = gnf.finalize(cstats if emb.jk else cstats[-1:], n)
         if readout is not None:
@@ -752,16 +791,13 @@ class StackProgram:
         entry, name = ((lib.glass_readout_max_train_w_f32, "glass_readout_max_train_w_f32") if mx else
                        (lib.glass_readout_train_w_f32, "glass_readout_train_w_f32"))
         mode_arg = () if mx else (_lib.POOL_MODES[pool_mode], )
-        _check(entry(jk.data_ptr(), jk.stride(0), saved, gn.weight.data_ptr(),
-                     gn.mean_scale.data_ptr(), pos.data_ptr(), B, Smax, *mode_arg,
-                     head.weight.data_ptr(), head.bias.data_ptr(), tgt.data_ptr(), loss_mode, K,
-                     _one(dev).data_ptr(), pooled.data_ptr(), logits.data_ptr(), loss.data_ptr(),
-                     djk.data_ptr(), djk.stride(0), head.weight.grad.data_ptr(),
-                     head.bias.grad.data_ptr(), st["acc"], gn.weight.grad.data_ptr(),
-                     gn.bias.grad.data_ptr(), gn.mean_scale.grad.data_ptr(), st["acc"], ws.data_ptr(),
-                     n, C, *largs, src, 0 if acc_ro is None else acc_ro.data_ptr(), REP_DENSE, sws,
-                     0 if self.loss_sum is None else self.loss_sum.data_ptr(), *wptrs, _stream()),
-               name)
+        _check(entry(*_pl(jk), saved, gn.weight.data_ptr(), gn.mean_scale.data_ptr(), pos.data_ptr(), B, Smax, *mode_arg,
+                     head.weight.data_ptr(), head.bias.data_ptr(), tgt.data_ptr(), loss_mode, K, _one(dev).data_ptr(),
+                     pooled.data_ptr(), logits.data_ptr(), loss.data_ptr(), *_pl(djk), head.weight.grad.data_ptr(),
+                     head.bias.grad.data_ptr(), st["acc"], gn.weight.grad.data_ptr(), gn.bias.grad.data_ptr(),
+                     gn.mean_scale.grad.data_ptr(), st["acc"], ws.data_ptr(), n, C, *largs, src,
+                     0 if acc_ro is None else acc_ro.data_ptr(), st["plan"].n_rep, sws,
+                     0 if self.loss_sum is None else self.loss_sum.data_ptr(), *wptrs, _stream()), name)
         st["djk"] = djk
         return loss, logits
 
@@ -773,9 +809,9 @@ class StackProgram:
     def _backward(self, st, dout, tail_hook, fused_opt):
         """tail_hook: called once every gradient except the embedding's and emb_gn's has been written (the data-parallel
         step starts the all-reduce of the small gradient bucket there, beside the rest of this backward pass)."""
-        emb = self.emb
+        emb, plan = self.emb, st["plan"]  # the forward's plan: nothing is decided again here
         n, H, L, p = st["n"], st["H"], st["L"], st["p"]
-        act = st["act"]
+        act, labels, blocks = st["act"], st["labels"], st["acc_blocks"]
         dev = st["mask"].device
         f32 = dict(dtype=torch.float32, device=dev)
         mask, jk = st["mask"], st["jk"]
@@ -792,124 +828,84 @@ class StackProgram:
         dh_next = None   # gradient w.r.t. the input of layer l+1 (= output of gns[l])
         npart = None     # backward column sums of gns[l], accumulated by layer l+1's trans data-gradient epilogue
         pending = []     # weight gradients whose partial sums are written but not yet reduced
-        nblk = -(-n // st["stat_rows"])
         f64 = dict(dtype=torch.float64, device=dev)
         for l in range(L - 1, -1, -1):
-            conv, rec = emb.convs[l], st["layers"][l]
+            conv, rec, lp = emb.convs[l], st["layers"][l], plan.layers[l]
             last = l + 1 == L
             # gradient w.r.t. the raw conv output c_l
             dc_src = None
             if last:
                 dc = djk[:, l * H:(l + 1) * H] if emb.jk else djk
-            elif (USE_GN_BWD_IN_COMB and npart.dtype == torch.int64 and _comb_eff_ok(conv, st.get("labels"), H, _comb_eff_ld(emb, H)) and
-                  _lib.load().glass_comb_eff_bwd_gn_src_supported(n, H)):
+            elif lp.gn_in_comb:
                 # gns[l]'s backward apply rides in the comb launch's operand loads (glass_gn_bwd_src): no launch, no dc
                 m = emb.gns[l]
                 ad = djk[:, l * H:(l + 1) * H] if emb.jk else None
-                dc_src = _lib.GnBwdSrc(npart.data_ptr(), _rep(npart), dh_next.data_ptr(), dh_next.stride(0), rec["c"].data_ptr(),
-                                       rec["c"].stride(0), 0 if ad is None else ad.data_ptr(), 0 if ad is None else ad.stride(0),
-                                       rec["nsaved"].data_ptr(), m.weight.data_ptr(), m.mean_scale.data_ptr(),
-                                       m.weight.grad.data_ptr(), m.bias.grad.data_ptr(), m.mean_scale.grad.data_ptr(), acc, act,
-                                       float(p), conv.call_base + 1)
+                dc_src = _lib.GnBwdSrc(npart.data_ptr(), _rep(npart), *_pl(dh_next), *_pl(rec["c"]), *_pl(ad), rec["nsaved"].data_ptr(),
+                                       m.weight.data_ptr(), m.mean_scale.data_ptr(), m.weight.grad.data_ptr(),
+                                       m.bias.grad.data_ptr(), m.mean_scale.grad.data_ptr(), acc, act, float(p), conv.call_base + 1)
                 dc = dh_next  # (shape carrier)
             else:
                 dc = torch.empty((n, H), **f32)
-                _GN(emb.gns[l]).bwd_from_stats(dh_next, rec["c"], rec["nsaved"], dc, npart, act, p, conv.call_base + 1,
-                                               addend=djk[:, l * H:(l + 1) * H] if emb.jk else None, acc=acc)
+                _GN(emb.gns[l]).bwd(dh_next, rec["c"], rec["nsaved"], dc, act, p, conv.call_base + 1,
+                                    addend=djk[:, l * H:(l + 1) * H] if emb.jk else None, acc=acc, partial=npart)
             din = torch.empty((n, 2 * H), **f32)  # [d g | d x_]
             # conv.gn's backward column sums come from this kernel's epilogue
-            labels = st.get("labels")
-            acc_all = st.get("gn_exact")
-            if acc_all is not None:
-                gpart = acc_all[2 * l]   # exact accumulators: the sums are final when the kernel is, no finalize launch
-            if acc_all is not None and _comb_eff_ok(conv, labels, H, _comb_eff_ld(emb, H)):
-                _comb_eff_bwd(dc, conv, mask, din, rec["g"], rec["h"], pending, acc,
-                              (gpart, rec["a"], rec["gsaved"], conv.gn.mean_scale, ACT_NONE, rec["pc"], conv.call_base), labels,
-                              dsrc_gn=dc_src)
-            elif acc_all is not None:
-                _dual_bwd(dc, None, conv._stack["comb"], mask, conv.z_ratio, ACT_NONE, 2 * H, None, din, rec["g"], rec["h"],
-                          pending, acc, gn=(gpart, rec["a"], rec["gsaved"], conv.gn.mean_scale, ACT_NONE, rec["pc"], conv.call_base))
-            elif _comb_eff_ok(conv, labels, H, _comb_eff_ld(emb, H)):
-                gpart = torch.empty((int(_lib.load().glass_comb_eff_blocks(n, H, labels.cap)), 2, H), **f64)
-                _comb_eff_bwd(dc, conv, mask, din, rec["g"], rec["h"], pending, acc,
-                              (gpart, rec["a"], rec["gsaved"], conv.gn.mean_scale, ACT_NONE, rec["pc"], conv.call_base), labels)
+            # (exact accumulators: the sums are final when the kernel is, no finalize launch)
+            gpart = blocks[lp.gn_bwd_acc] if lp.gn_bwd_acc >= 0 else torch.empty((lp.gn_bwd_blocks, 2, H), **f64)
+            gn = (gpart, rec["a"], rec["gsaved"], conv.gn.mean_scale, ACT_NONE, rec["pc"], conv.call_base)
+            if lp.comb_bwd == "eff":
+                _comb_eff_bwd(dc, conv, mask, din, rec["g"], rec["h"], pending, acc, gn, labels, dsrc_gn=dc_src)
             else:
-                gpart = torch.empty((nblk, 2, H), **f64)
-                _dual_bwd(dc, None, conv._stack["comb"], mask, conv.z_ratio, ACT_NONE, 2 * H, None, din, rec["g"], rec["h"],
-                          pending, acc, gn=(gpart, rec["a"], rec["gsaved"], conv.gn.mean_scale, ACT_NONE, rec["pc"], conv.call_base))
+                _dual_bwd(plan.fused_bwd, dc, None, conv._stack["comb"], mask, conv.z_ratio, ACT_NONE, 2 * H, None, din, rec["g"],
+                          rec["h"], pending, acc, gn=gn)
             da = torch.empty((n, H), **f32)
-            _GN(conv.gn).bwd_from_stats(din[:, :H], rec["a"], rec["gsaved"], da, gpart, ACT_NONE, rec["pc"], conv.call_base,
-                                        acc=acc)
+            _GN(conv.gn).bwd(din[:, :H], rec["a"], rec["gsaved"], da, ACT_NONE, rec["pc"], conv.call_base, acc=acc, partial=gpart)
             dm = conv.adj.bwd.spmm(da)
             dh = torch.empty((n, H), **f32)
             # layer 0 on the table path: the epilogue applies emb_gn's dropout mask (call id 1); layers above: the
             # epilogue accumulates the backward column sums of gns[l-1], whose output this gradient belongs to
-            drop = (p, 1) if (l == 0 and "emb_table" in st) else None
+            drop = (p, 1) if (l == 0 and plan.embed != "plain") else None
             gn = None
             if l > 0:
                 below, cb = st["layers"][l - 1], emb.convs[l - 1]
-                npart = acc_all[2 * l - 1] if acc_all is not None else torch.empty((nblk, 2, H), **f64)
+                npart = blocks[lp.gns_bwd_acc] if lp.gns_bwd_acc >= 0 else torch.empty((plan.dense_blocks, 2, H), **f64)
                 gn = (npart, below["c"], below["nsaved"], emb.gns[l - 1].mean_scale, act, p, cb.call_base + 1)
-            _dual_bwd(dm, rec["T"], conv._stack["trans"], mask, conv.z_ratio, act, H, din[:, H:], dh, rec["h"], None, pending,
-                      acc, drop, gn)
+            _dual_bwd(plan.fused_bwd, dm, rec["T"], conv._stack["trans"], mask, conv.z_ratio, act, H, din[:, H:], dh, rec["h"], None,
+                      pending, acc, drop, gn)
             dh_next = dh
             st["layers"][l] = None  # release this layer's activations
         W = emb.input_emb.weight
         self.applied_optimizer = False
-        if st.get("unlabeled"):
-            # no GraphNorm behind the embedding: the selection product IS the table's gradient (layer 0's data-gradient
-            # epilogue applied the embedding's dropout mask already)
-            _reduce_pending(pending, None)
-            if tail_hook is not None:
-                tail_hook()
-            sel = st["emb_table"]
-            if acc:
-                W.grad.add_(sel.op.spmm(dh_next))
-            else:
-                sel.op.spmm(dh_next, out=W.grad)
-            return
-        gn0 = emb.emb_gn
-        fused_tail = "emb_table" in st and USE_FUSED_TAIL
-        # the deferred weight-gradient reductions — and, on the table path, the selection product of the embedding
+        fused_tail = plan.tail == "fused"
+        # the deferred weight-gradient reductions — and, on the fused tail, the selection product of the embedding
         # backward in the same launch (both only wait for the end of the chain above)
         prod = _reduce_pending(pending, (st["emb_table"], dh_next) if fused_tail else None)
         if tail_hook is not None:
             tail_hook()
-        if fused_tail:
-            # the selection product's partial-row sums, the table backward and — with fused_opt (optim.FlatAdam) — Adam over
-            # the whole arena as ONE launch
-            sel, arena = st["emb_table"], emb._glass_arena
-            offs = [arena.offset_of(t) for t in (W, gn0.weight, gn0.bias, gn0.mean_scale)]
-            opt_ok = fused_opt is not None and all(o is not None for o in offs) and fused_opt.fusable() and acc == 0
-            G, ws, rrows, n_red = prod
-            oargs = (*fused_opt.fused_args(), *offs) if opt_ok else (0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0)
-            _check(_lib.load().glass_embed_norm_bwd_adam_f32(G.data_ptr(), W.data_ptr(), W.shape[0], sel.op.rowptr.data_ptr(),
-                                                             gn0.weight.data_ptr(), gn0.mean_scale.data_ptr(),
-                                                             st["emb_saved"].data_ptr(), W.grad.data_ptr(), acc,
-                                                             gn0.weight.grad.data_ptr(), gn0.bias.grad.data_ptr(),
-                                                             gn0.mean_scale.grad.data_ptr(), acc, H, ws, rrows, n_red,
-                                                             *oargs, _stream()),
-                   "glass_embed_norm_bwd_adam_f32")
-            self.applied_optimizer = opt_ok
-            return
-        if "emb_table" in st:
-            sel = st["emb_table"]
-            G = sel.op.spmm(dh_next)  # [V,H]: per table row, the sum of its nodes' (masked) gradients, on K1
-            _check(_lib.load().glass_embed_norm_bwd_f32(G.data_ptr(), W.data_ptr(), W.shape[0], sel.op.rowptr.data_ptr(),
-                                                        gn0.weight.data_ptr(), gn0.mean_scale.data_ptr(),
-                                                        st["emb_saved"].data_ptr(), W.grad.data_ptr(), acc,
-                                                        gn0.weight.grad.data_ptr(), gn0.bias.grad.data_ptr(),
-                                                        gn0.mean_scale.grad.data_ptr(), acc, H, _stream()),
-                   "glass_embed_norm_bwd_f32")
-            return
-        dh0 = torch.empty((n, H), **f32)
-        _GN(gn0).bwd(dh_next, st["h0"], st["emb_saved"], dh0, ACT_NONE, p, 1, acc=acc)
-        # embedding backward: dW (+)= S^T @ dh0 on K1
-        if acc:
-            W.grad.add_(emb._selection(st["x_flat"]).op.spmm(dh0))
-        else:
-            emb._selection(st["x_flat"]).op.spmm(dh0, out=W.grad)
-
+        if plan.tail == "unlabeled":
+            # no GraphNorm behind the embedding: the selection product IS the table's gradient (layer 0's data-gradient
+            # epilogue applied the embedding's dropout mask already)
+            return _table_grad(st["emb_table"], dh_next, W, acc)
+        gn0 = emb.emb_gn
+        if plan.tail == "plain":
+            dh0 = torch.empty((n, H), **f32)
+            _GN(gn0).bwd(dh_next, st["h0"], st["emb_saved"], dh0, ACT_NONE, p, 1, acc=acc)
+            return _table_grad(emb._selection(st["x_flat"]), dh0, W, acc)
+        sel = st["emb_table"]
+        # G [V,H]: per table row, the sum of its nodes' (masked) gradients, on K1 (fused tail: still in partial rows)
+        G, *red = prod if fused_tail else (sel.op.spmm(dh_next), )
+        targs = (G.data_ptr(), W.data_ptr(), W.shape[0], sel.op.rowptr.data_ptr(), gn0.weight.data_ptr(), gn0.mean_scale.data_ptr(),
+                 st["emb_saved"].data_ptr(), W.grad.data_ptr(), acc, gn0.weight.grad.data_ptr(), gn0.bias.grad.data_ptr(),
+                 gn0.mean_scale.grad.data_ptr(), acc, H)
+        if not fused_tail:
+            return _check(_lib.load().glass_embed_norm_bwd_f32(*targs, _stream()), "glass_embed_norm_bwd_f32")
+        # the selection product's partial-row sums, the table backward and — with fused_opt (optim.FlatAdam) — Adam over
+        # the whole arena as ONE launch
+        offs = [emb._glass_arena.offset_of(t) for t in (W, gn0.weight, gn0.bias, gn0.mean_scale)]
+        opt_ok = fused_opt is not None and all(o is not None for o in offs) and fused_opt.fusable() and acc == 0
+        oargs = (*fused_opt.fused_args(), *offs) if opt_ok else (0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0)
+        _check(_lib.load().glass_embed_norm_bwd_adam_f32(*targs, *red, *oargs, _stream()), "glass_embed_norm_bwd_adam_f32")
+        self.applied_optimizer = opt_ok
 
     # ---------------------------------------------------------------------------------------------
     def written_params(self, head):
@@ -943,6 +939,14 @@ class StackProgram:
         return loss, logits
 
 
+def _table_grad(sel, x, W, acc):
+    """embedding backward: dW (+)= S^T @ x on K1 (sel: the graph.Selection of the batch's feature column)"""
+    if acc:
+        W.grad.add_(sel.op.spmm(x))
+    else:
+        sel.op.spmm(x, out=W.grad)
+
+
 _ones = {}
 
 
@@ -961,7 +965,7 @@ def step_supported(model, loss_fn):
     from . import losses
     from .models import EmbZGConv, PoolModule
     emb = getattr(model, "conv", None)
-    if not (USE_READOUT and isinstance(emb, EmbZGConv) and StackProgram.supported(emb) and emb.training):
+    if not (isinstance(emb, EmbZGConv) and StackProgram.supported(emb) and emb.training):
         return False
     pool, head = model.pools[0], model.preds[0]
     if not (isinstance(pool, PoolModule) and pool.trans_fn is None and pool.mode in ("sum", "mean", "size", "max")):
@@ -970,12 +974,7 @@ def step_supported(model, loss_fn):
             head.bias.grad is not None and losses.fusable_spec(loss_fn) is not None):
         return False
     C = emb.gns[-1].weight.shape[0]
-    lib, K = _lib.load(), head.weight.shape[0]
-    if head.weight.shape[1] != C:
-        return False
-    if pool.mode == "max":
-        return bool(lib.glass_readout_max_supported(C, K))
-    return bool(lib.glass_readout_supported(C, K, _lib.POOL_MODES[pool.mode]))
+    return head.weight.shape[1] == C and _readout_ok(pool.mode, C, head.weight.shape[0])
 
 
 def covers_arena(model, arena):
@@ -993,10 +992,10 @@ def _program(emb):
 
 def loss_and_grads(model, loss_fn, x, edge_index, edge_weight, pos, z, target, overwrite=False, tail_hook=None, labels=None,
                    fused_opt=None):
-    """fused_opt (optim.FlatAdam over the model's arena, overwrite mode only): the optimizer step rides in the backward's
-    last launch when it can — `applied_optimizer(model)` tells whether it did (else call fused_opt.step())."""
     """(loss, logits) of model(x, ..., pos, z) under loss_fn, gradients accumulated in place (see step_supported).
-    z = "pos": label the nodes listed in pos (what utils.MaxZOZ(x, pos) would mark) without materialising z."""
+    z = "pos": label the nodes listed in pos (what utils.MaxZOZ(x, pos) would mark) without materialising z.
+    fused_opt (optim.FlatAdam over the model's arena, overwrite mode only): the optimizer step rides in the backward's
+    last launch when it can — `applied_optimizer(model)` tells whether it did (else call fused_opt.step())."""
     from . import losses
     emb = model.conv
     if x.dim() != 3 or x.shape[1] != 1 or x.shape[2] != 1:

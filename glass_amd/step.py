@@ -6,8 +6,10 @@ form, ~0.33 ms of GPU time), so eager launches are host-bound; every kernel in l
 caller's stream (no allocation, no sync, no memset / memcpy nodes), which makes the whole step capturable:
 labels -> forward -> loss -> backward -> [all-reduce] -> Adam.  Dropout masks still change every replay
 because the dropout (seed, step) pair lives in device memory and is advanced by a captured kernel.
-With more than one rank the collectives stay outside the graph (captured forward/backward, eager RCCL exchange of
-the gradient arena, eager fused Adam launches).  The exchange is bucketed (dist.GradExchange): the small bucket
+With more than one rank the RCCL exchange of the gradient arena and Adam are captured with the step (one replay per
+step) once a replay has reproduced an eager step on every rank (CAPTURE_COLLECTIVE, _verify_collective_capture); where
+the capture is refused or fails that check, the collectives stay outside the graph (captured forward/backward, eager
+exchange, eager fused Adam launches).  The exchange is bucketed (dist.GradExchange): the small bucket
 (layer / head parameters) is all-reduced; an embedding-sized bucket (`--use_nodeid`) is reduce-scattered, Adam updates
 this rank's shard, and the updated parameter shards are all-gathered.  With such a bucket the backward pass is captured
 as TWO graphs cut where the small bucket becomes final, and its all-reduce runs on a second stream beside the rest of
