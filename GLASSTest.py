@@ -26,7 +26,8 @@ import datasets
 from impl import SubGDataset, config, metrics, models, train, utils
 
 SYNTHETIC_SETS = ("density", "component", "cut_ratio", "coreness")
-POOLS = {"mean": models.MeanPool, "max": models.MaxPool, "sum": models.AddPool, "size": models.SizePool}
+POOLS = {"mean": models.MeanPool, "max": models.MaxPool, "sum": models.AddPool, "size": models.SizePool,
+         "attn": models.AttnPool}  # attn (extension): a learned readout, constructed with the pooled width
 
 
 def parse_args(argv=None):
@@ -46,6 +47,8 @@ def parse_args(argv=None):
     p.add_argument("--class_weight", type=str, default="none", choices=("none", "balanced"),
                    help="(extension) balanced: class weights (multi-class) / pos_weight (binary, multi-label) from the training "
                         "split's label counts, applied inside the fused loss (default: none)")
+    p.add_argument("--pool", type=str, default=None, choices=tuple(POOLS),
+                   help="(extension) readout instead of the config file's `pool` (default: the config's value)")
     args = p.parse_args(argv)
     if args.clip is not None and not args.clip > 0:
         p.error("--clip must be positive")
@@ -133,8 +136,10 @@ class Run:
                 if h > emb.shape[1]:  # (a width no kernel family serves runs zero-padded: glass_amd/widths.py)
                     emb = torch.nn.functional.pad(emb, (0, h - emb.shape[1]))
                 conv.input_emb = nn.Embedding.from_pretrained(emb, freeze=False)
-            mlp = nn.Linear(h * conv_layer if jk else h, self.output_channels)
-            return models.GLASS(conv, nn.ModuleList([mlp]), nn.ModuleList([POOLS[pool]()]))
+            width = h * conv_layer if jk else h  # what the readout hands the head
+            mlp = nn.Linear(width, self.output_channels)
+            pool_fn = POOLS[pool](width) if pool == "attn" else POOLS[pool]()
+            return models.GLASS(conv, nn.ModuleList([mlp]), nn.ModuleList([pool_fn]))
 
         # widths outside the kernel families (every shipped config is inside) run at the next family width, zero padded: exact
         from glass_amd import widths
@@ -239,6 +244,8 @@ def main(argv=None):
     with open(f"config/{args.dataset.replace(':', '_')}.yml") as f:
         params = yaml.safe_load(f)
     print("params", params, flush=True)
+    if args.pool is not None:
+        params["pool"] = args.pool
     run.split()
     return run.test(**params)
 

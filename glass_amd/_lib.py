@@ -113,6 +113,12 @@ SIGNATURES = {
     "glass_pair_pool_ws_bytes": (c_int64, [_I, _I]),
     "glass_segment_pool_bwd_exact_ws_bytes": (c_int64, [_I, _I, _I]),
     "glass_segment_pool_bwd_exact_f32": (c_int, [_P, _I, _P, _I, _I, c_int, _P, _I, _I, _I, _P, _P]),
+    "glass_attn_pool_wave_rows": (c_int64, []),
+    "glass_attn_pool_stage_floats": (c_int64, []),
+    "glass_attn_pool_score_rows": (c_int64, []),
+    "glass_attn_pool_f32": (c_int, [_P, _I, _P, _I, _I, _P, _P, _I, _P, _I, _I, _P]),
+    "glass_attn_pool_bwd_ws_bytes": (c_int64, [_I, _I, _I, _I]),
+    "glass_attn_pool_bwd_f32": (c_int, [_P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, c_int, _I, _I, _P, _P]),
     "glass_pair_pool_f32": (c_int, [_P, _I, _P, _I, c_int, _P, _I, _I, _I, _P]),
     "glass_pair_pool_bwd_f32": (c_int, [_P, _I, _P, _I, c_int, _P, _I, _I, _I, _P, _P]),
     "glass_dense_caps_query": (c_int, [_I, _P]),

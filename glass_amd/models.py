@@ -7,6 +7,7 @@ torch; there is no CPU path.
 Reference map (file:line under /root/reference):
   Seq 10-24 · MLP 27-80 · buildAdj 83-111 · GLASSConv 114-174 · EmbZGConv 177-272 ·
   PoolModule/AddPool/MaxPool/MeanPool/SizePool 275-319 · GLASS 322-355   (impl/models.py)
+Not in the reference: AttnPool (attention readout, pool "attn").
 """
 import torch
 import torch.nn as nn
@@ -364,6 +365,23 @@ class SizePool(AddPool):
     mode = "size"
 
 
+class AttnPool(PoolModule):
+    """Attention readout (an extension: the reference has no learned pool): out[b] = sum_j alpha[b, j] * x_j with alpha the
+    softmax over the subgraph's nodes of gate(x_j) (ops.attn_pool, csrc/pool_attn.hip).  The gate has no bias — it would
+    cancel in the softmax — and starts at ZERO: the pool is then exactly mean pooling."""
+    mode = "attn"
+
+    def __init__(self, in_channels, trans_fn=None):
+        super().__init__(None, trans_fn)
+        self.gate = nn.Linear(in_channels, 1, bias=False)
+        nn.init.zeros_(self.gate.weight)
+
+    def forward(self, x, batch):
+        if self.trans_fn is not None:
+            x = self.trans_fn(x)
+        return ops.attn_pool(x, batch2pad(batch), self.gate.weight)
+
+
 class GLASS(nn.Module):
     """EmbZGConv + per-target pooling and prediction heads (`preds[id]`, `pools[id]`)."""
     def __init__(self, conv: EmbZGConv, preds: nn.ModuleList, pools: nn.ModuleList):
@@ -399,6 +417,8 @@ class GLASS(nn.Module):
         return torch.stack(embs, dim=1).mean(dim=1)
 
     def Pool(self, emb, subG_node, pool):
+        if isinstance(pool, AttnPool) and pool.trans_fn is None:
+            return ops.attn_pool(emb, subG_node, pool.gate.weight)
         if isinstance(pool, PoolModule) and pool.trans_fn is None and pool.mode is not None:
             return ops.segment_pool(emb, subG_node, pool.mode)
         from .utils import pad2batch

@@ -733,3 +733,59 @@ class SegmentPoolFn(torch.autograd.Function):
 
 def segment_pool(emb, pos, mode):
     return SegmentPoolFn.apply(emb, pos, mode)
+
+
+# ---------------------------------------------------------------------------------------------
+# K7a  attention pooling (pool "attn": an extension, csrc/pool_attn.hip)
+# ---------------------------------------------------------------------------------------------
+class AttnPoolFn(torch.autograd.Function):
+    """out[b] = sum_j alpha[b, j] * emb[pos[b, j]], alpha = softmax over the non-padding nodes of pos[b] of emb[node] . w
+    (one launch; alpha and out are what the backward keeps — it recomputes nothing of the softmax)."""
+    @staticmethod
+    def forward(ctx, emb, pos, weight):
+        _need_gpu(emb, pos, weight)
+        emb, lde = _rows(emb)
+        pos = pos.contiguous()
+        if pos.dtype != torch.int64:
+            pos = pos.to(torch.int64)
+        n, C = emb.shape
+        if weight.numel() != C or weight.dtype != torch.float32:
+            raise GlassHipError(f"attn_pool: gate weight {tuple(weight.shape)} {weight.dtype} for embeddings of width {C}")
+        w = weight.reshape(-1).contiguous()
+        B, Smax = pos.shape
+        if B == 0 or Smax == 0:  # (the entry launches nothing: rows without entries pool to 0)
+            out = torch.zeros((B, C), dtype=torch.float32, device=emb.device)
+        else:
+            out = torch.empty((B, C), dtype=torch.float32, device=emb.device)
+        alpha = torch.empty((B, Smax), dtype=torch.float32, device=emb.device)
+        rc = _lib.load().glass_attn_pool_f32(emb.data_ptr(), lde, pos.data_ptr(), B, Smax, w.data_ptr(), out.data_ptr(), C,
+                                             alpha.data_ptr(), n, C, _stream())
+        _lib.check(rc, "glass_attn_pool_f32")
+        ctx.save_for_backward(emb, pos, w, alpha, out)
+        ctx.cfg = (lde, tuple(weight.shape))
+        ctx.mark_non_differentiable(alpha)
+        return out, alpha
+
+    @staticmethod
+    def backward(ctx, dout, _dalpha):
+        emb, pos, w, alpha, out = ctx.saved_tensors
+        lde, wshape = ctx.cfg
+        dout, ldd = _rows(dout)
+        n, C = emb.shape
+        B, Smax = pos.shape
+        lib = _lib.load()
+        demb = torch.empty((n, C), dtype=torch.float32, device=dout.device)
+        dw = torch.empty(C, dtype=torch.float32, device=dout.device)
+        ws = _scratch(("attn_pool", n, B, Smax, C), dout.device, lib.glass_attn_pool_bwd_ws_bytes(n, B, Smax, C))
+        rc = lib.glass_attn_pool_bwd_f32(dout.data_ptr(), ldd, emb.data_ptr(), lde, pos.data_ptr(), B, Smax, w.data_ptr(),
+                                         alpha.data_ptr(), out.data_ptr(), C, demb.data_ptr(), C, dw.data_ptr(), 0, n, C,
+                                         ws.data_ptr(), _stream())
+        _lib.check(rc, "glass_attn_pool_bwd_f32")
+        return demb, None, dw.view(wshape)
+
+
+def attn_pool(emb, pos, weight, return_alpha=False):
+    """Attention readout of the padded node matrix `pos` ([B, Smax] int64, -1 = padding) with the gate weight `weight`
+    ([C] or [1, C], no bias): [B, C] — and the attention weights [B, Smax] (no gradient) with return_alpha."""
+    out, alpha = AttnPoolFn.apply(emb, pos, weight)
+    return (out, alpha) if return_alpha else out

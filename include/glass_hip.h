@@ -331,6 +331,37 @@ int glass_pair_pool_bwd_f32(const float* dout, int64_t ldd, const int64_t* pairs
                             int64_t lde, int64_t n_nodes, int64_t C, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K7a attention pooling (pool `attn`: an EXTENSION, the reference has no learned readout) — sits beside the pool family
+ *     of impl/models.py:275-319 and the call that applies a pool, impl/models.py:346-350.  Same padded-matrix
+ *     convention as K7 (-1 = padding anywhere in a row, a node named twice counts twice, ids >= n_nodes are skipped like
+ *     padding inside the kernels, an all-padding row gives 0); gate weight w [C], no gate bias (it cancels in the softmax):
+ *         s[b,j]   = dot(emb[pos[b,j], :], w)
+ *         alpha    = softmax of s over the valid j of row b (max-subtracted, expf), 0 at padding
+ *         out[b,:] = sum_j alpha[b,j] * emb[pos[b,j], :]
+ *     alpha [B, Smax] is written in full; with out it is the backward's only saved state (nothing is recomputed there).
+ *     Backward: ds[b,j] = alpha[b,j] * (dot(dout[b], emb[pos[b,j]]) - dot(dout[b], out[b]));
+ *         demb[n,:] = sum over the entries naming n of (alpha * dout[b,:] + ds * w)  — EVERY row written (no zero-fill);
+ *         dw (+)= sum_{b,j} ds[b,j] * emb[pos[b,j], :]                               — accumulated when acc_dw != 0.
+ *     No float atomic, bitwise repeatable: fixed summation orders per row; dw from per-subgraph shares in `ws` folded in b
+ *     order by a second launch; demb from node buckets summed in exact fixed point.  1 <= C <= 4096 (else
+ *     GLASS_E_UNSUPPORTED); B == 0 or Smax == 0 is a valid no-op (the backward then zero-fills demb, and dw unless acc_dw).
+ *     Plain 64-bit addressing: no 32-bit buffer-offset limit on n_nodes * lde.  `ws`: glass_attn_pool_bwd_ws_bytes bytes,
+ *     16-byte aligned, need not be initialised.  Launches: forward 1, backward 7.
+ *     Dispatch thresholds (accessors): rows of <= wave_rows entries run one wave per subgraph, longer ones a 256-lane
+ *     workgroup; Smax * C <= stage_floats keeps the gathered rows in LDS (one gather per entry), beyond it the weighted sum
+ *     gathers again; Smax <= score_rows keeps the scores in LDS, beyond it they wait in alpha.
+ * ---------------------------------------------------------------------------------------- */
+int64_t glass_attn_pool_wave_rows(void);
+int64_t glass_attn_pool_stage_floats(void);
+int64_t glass_attn_pool_score_rows(void);
+int glass_attn_pool_f32(const float* emb, int64_t lde, const int64_t* pos, int64_t B, int64_t Smax, const float* w, float* out,
+                        int64_t ldo, float* alpha, int64_t n_nodes, int64_t C, void* stream);
+int64_t glass_attn_pool_bwd_ws_bytes(int64_t n_nodes, int64_t B, int64_t Smax, int64_t C);
+int glass_attn_pool_bwd_f32(const float* dout, int64_t ldd, const float* emb, int64_t lde, const int64_t* pos, int64_t B,
+                            int64_t Smax, const float* w, const float* alpha, const float* out, int64_t ldo, float* demb,
+                            int64_t ldde, float* dw, int acc_dw, int64_t n_nodes, int64_t C, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K9  link-prediction head of the pre-training path on node pairs, hidden 64 (glass_pair_head_supported)
  *     replaces EdgeGNN.Pool + MLP(hidden, hidden, 1, 2) + BCEWithLogitsLoss and their autograd
  *     (impl/models.py:497-509, 33-50; GNNEmb.py:94-99, 129-130, 144: 131 072 pairs per step):
