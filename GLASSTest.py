@@ -38,6 +38,9 @@ def parse_args(argv=None):
     p.add_argument("--use_one", action="store_true")
     p.add_argument("--use_nodeid", action="store_true")
     p.add_argument("--use_maxzeroone", action="store_true")
+    p.add_argument("--use_zeroone", action="store_true",
+                   help="(extension) exact zero-one labels: every subgraph of a batch labeled on its own replica of the graph "
+                        "(utils.ZeroOneZ; about batch-size times the work and memory of --use_maxzeroone)")
     p.add_argument("--repeat", type=int, default=1)
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--use_seed", action="store_true")
@@ -50,6 +53,8 @@ def parse_args(argv=None):
     p.add_argument("--pool", type=str, default=None, choices=tuple(POOLS),
                    help="(extension) readout instead of the config file's `pool` (default: the config's value)")
     args = p.parse_args(argv)
+    if args.use_zeroone and args.use_maxzeroone:
+        p.error("--use_zeroone and --use_maxzeroone are mutually exclusive")
     if args.clip is not None and not args.clip > 0:
         p.error("--clip must be positive")
     return args
@@ -107,9 +112,10 @@ class Run:
 
     def loaders(self, batch_size):
         """(train, valid, test) loaders.  With --use_maxzeroone every batch is labeled by utils.MaxZOZ and the training
-        loader drops the last partial batch; without it plain loaders are used and nothing is dropped.  All shuffle."""
-        if self.args.use_maxzeroone:
-            make = functools.partial(SubGDataset.ZGDataloader, z_fn=utils.MaxZOZ, shuffle=True)
+        loader drops the last partial batch (--use_zeroone: the same with utils.ZeroOneZ); without it plain loaders are used and nothing is dropped.  All shuffle."""
+        if self.args.use_maxzeroone or getattr(self.args, "use_zeroone", False):
+            z_fn = utils.ZeroOneZ if getattr(self.args, "use_zeroone", False) else utils.MaxZOZ
+            make = functools.partial(SubGDataset.ZGDataloader, z_fn=z_fn, shuffle=True)
             # (under torch.distributed the TRAINING loader hands every rank its slice of each batch — subgraph-batch data
             # parallelism, glass_amd/dist.py; evaluation loaders are never sharded, so scores agree on every rank)
             from glass_amd import dist as gdist

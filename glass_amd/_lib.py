@@ -219,6 +219,18 @@ SIGNATURES = {
     "glass_eval_f1_counts_f32": (c_int, [_P, _I, _P, _I, _I, _I, c_int, _P, _P]),
     "glass_eval_auroc_supported": (c_int, [_I, _I]),
     "glass_eval_auroc_counts_f32": (c_int, [_P, _I, _P, _I, _I, _I, _P, _P]),
+    # exact zero-one labels: R replicas of one graph (labels_rep.hip, spmm_rep.hip, graphnorm_rep.hip)
+    "glass_zeroone_labels_u8": (c_int, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "glass_spmm_rep_max_replicas": (c_int64, []),
+    "glass_spmm_rep_ws_bytes": (c_int64, [_P, _I, _I]),
+    "glass_spmm_csr_rep_f32": (c_int, [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "glass_graphnorm_rep_max_replicas": (c_int64, []),
+    "glass_graphnorm_rep_row_block": (c_int64, [_I, c_int]),
+    "glass_graphnorm_rep_ws_bytes": (c_int64, [_I, _I, _I]),
+    "glass_graphnorm_rep_fwd_f32": (c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, c_float, _P, c_int, c_float, _P,
+                                            c_uint64, _P, _P]),
+    "glass_graphnorm_rep_bwd_f32": (c_int, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, c_int,
+                                            c_int, c_float, _P, c_uint64, _P, _P]),
 }
 
 _lib = None

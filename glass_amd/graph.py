@@ -42,6 +42,7 @@ class CSROperand:
         else:
             self.plan = torch.from_numpy(plan).pin_memory().to(rowptr.device, non_blocking=True)
         self._ws = {}
+        self._retired_ws = []
 
     @property
     def nnz(self):
@@ -73,6 +74,40 @@ class CSROperand:
                                             self.header.ctypes.data, self.plan.data_ptr(),
                                             self.workspace(H).data_ptr(), torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "glass_spmm_csr_f32")
+        return out
+
+    def spmm_rep(self, x, R, x_rep_stride=None, out=None, y_rep_stride=None):
+        """Y[r] = M @ X[r] for R replicas in one launch (glass_spmm_csr_rep_f32): x holds replica r's rows from row
+        r * x_rep_stride (default n_cols: replica-major [R * n_cols, H]), out likewise from r * y_rep_stride (default
+        n_rows).  Same plan and indices as `spmm`; replica r has the bits `spmm` gives on its slice."""
+        assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32 and x.is_cuda
+        R = int(R)
+        xs = self.n_cols if x_rep_stride is None else int(x_rep_stride)
+        ys = self.n_rows if y_rep_stride is None else int(y_rep_stride)
+        assert R == 0 or x.shape[0] >= (R - 1) * xs + self.n_cols, f"X has {x.shape[0]} rows for {R} replicas of {self.n_cols}"
+        H = x.shape[1]
+        if out is None:
+            out = torch.empty((R * ys, H), dtype=torch.float32, device=x.device)
+        assert out.stride(1) == 1 and out.shape[1] == H and (R == 0 or out.shape[0] >= (R - 1) * ys + self.n_rows)
+        lib = _lib.load()
+        key = ("rep", H, _ws_branch)  # one buffer per width, grown when a call needs more replicas' partial rows
+        nbytes = lib.glass_spmm_rep_ws_bytes(self.header.ctypes.data, H, R)
+        if nbytes < 0:
+            raise _lib.GlassHipError("bad plan header")
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() * 4 < nbytes:
+            if ws is not None:
+                self._retired_ws.append(ws)  # (a captured graph may still launch with this pointer: never handed back)
+            ws = self._ws[key] = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=self.rowptr.device)
+        ldx = x.stride(0) if x.shape[0] > 1 else max(H, x.stride(0))
+        ldy = out.stride(0) if out.shape[0] > 1 else max(H, out.stride(0))
+        rc = lib.glass_spmm_csr_rep_f32(self.rowptr.data_ptr(), self.col.data_ptr(), self.val.data_ptr(), x.data_ptr(), ldx, xs,
+                                        out.data_ptr(), ldy, ys, self.n_rows, H, R, self.header.ctypes.data,
+                                        self.plan.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if rc == -3:  # GLASS_E_UNSUPPORTED: too many replicas, or too much memory, for one launch
+            msg = lib.glass_last_error_string().decode(errors="replace")
+            raise _lib.GlassHipError(f"glass_spmm_csr_rep_f32: {msg}; run the replicas in smaller groups (EmbZGConv.replica_chunk)")
+        _lib.check(rc, "glass_spmm_csr_rep_f32")
         return out
 
 

@@ -29,7 +29,9 @@ class GraphNorm(nn.Module):
     """GraphNorm (PyG 1.7.2 semantics): parameters `weight`, `bias`, `mean_scale` initialised to 1, 0, 1.
     batch=None normalises over all rows as one graph, and `forward` then optionally fuses the ELU and the inverted dropout
     that follow every GraphNorm in the reference (models.py:166,251,258-259).  With `batch` every graph of a batch is
-    normalised over its own rows (ops.graphnorm_seg); the activation is still fused, dropout is not."""
+    normalised over its own rows (ops.graphnorm_seg); the activation is still fused, dropout is not.  With an ops.Replicas as
+    `batch` the rows are R replicas of ONE graph (exact zero-one labels): each is normalised over its own N rows by the
+    whole-graph kernels' replicated form (ops.graphnorm_rep), activation and dropout fused as for batch=None."""
     def __init__(self, in_channels, eps=1e-5):
         super().__init__()
         self.in_channels, self.eps = in_channels, eps
@@ -48,6 +50,8 @@ class GraphNorm(nn.Module):
         int32 row offsets [B + 1] of the graphs (what seg.SegAdj carries), which costs nothing.  An unsorted batch raises
         ValueError where it is looked at (without batch_size)."""
         direct = getattr(self, "_direct_grad", False)
+        if isinstance(batch, ops.Replicas):  # R replicas of one graph, N rows each, every replica over its own rows
+            return ops.graphnorm_rep(x, batch, self.weight, self.bias, self.mean_scale, self.eps, act, p_drop, call_id, direct)
         if batch is None:
             return ops.graphnorm(x, self.weight, self.bias, self.mean_scale, self.eps, act, p_drop, call_id, direct)
         if p_drop > 0:
@@ -172,10 +176,17 @@ class GLASSConv(nn.Module):
             lin.reset_parameters()
         self.gn.reset_parameters()
 
-    def forward(self, x_, edge_index, edge_weight, mask, out=None):
-        """`out` (optional, fused path only): a preallocated [N,H] view (a slice of the JK buffer) to write into."""
+    def forward(self, x_, edge_index, edge_weight, mask, out=None, batch=None):
+        """`out` (optional, fused path only): a preallocated [N,H] view (a slice of the JK buffer) to write into.
+        `batch`: an ops.Replicas when x_ holds R replicas of the graph's rows (replica-major, [R * N, H]) with one label byte
+        per replica row: the aggregation and the GraphNorm then run per replica (ops.spmm_rep, ops.graphnorm_rep); the dense
+        calls key only on the row's label byte and take the R * N rows as they are."""
         if self.adj is None:
-            self.adj = buildAdj(edge_index, edge_weight, x_.shape[0], self.aggr)
+            self.adj = buildAdj(edge_index, edge_weight, x_.shape[0] if batch is None else batch.N, self.aggr)
+        if batch is not None and x_.shape[0] != batch.R * batch.N:
+            raise ValueError(f"GLASSConv: {x_.shape[0]} rows for {batch!r}")
+        agg = (lambda m: ops.spmm(self.adj, m)) if batch is None else (lambda m: ops.spmm_rep(self.adj, m, batch.R))
+        rep = {} if batch is None else {"rep": batch}  # (a training pass collects the weight gradients replica by replica)
         if mask.dtype != torch.uint8:
             mask = mask.reshape(-1).to(torch.uint8)
         p = self.dropout if self.training else 0.0
@@ -186,20 +197,20 @@ class GLASSConv(nn.Module):
                 self.trans_fns[0].weight.shape == (H, H) and ops.dual_linear_supported(H) and ops.USE_FUSED_DENSE):
             # fused dense path: Linear pair + ELU + mix in one MFMA kernel each; no cat, no [N,2H] round trips
             m = ops.dual_linear_mix(x_, None, self.trans_fns[1], self.trans_fns[0], mask, self.z_ratio, code,
-                                    stack["trans"])
-            a = ops.spmm(self.adj, m)
-            g = self.gn(a, p_drop=p, call_id=self.call_base)
+                                    stack["trans"], **rep)
+            a = agg(m)
+            g = self.gn(a, batch=batch, p_drop=p, call_id=self.call_base)
             return ops.dual_linear_mix(g, x_, self.comb_fns[1], self.comb_fns[0], mask, self.z_ratio, ACT_NONE,
-                                       stack["comb"], out)
+                                       stack["comb"], out, **rep)
         # both weight sets in one GEMM: T = [f1 | f0]
-        T = ops.stacked_linear(x_, self.trans_fns[1], self.trans_fns[0], stack.get("trans"))
+        T = ops.stacked_linear(x_, self.trans_fns[1], self.trans_fns[0], stack.get("trans"), **rep)
         if code is None:
             T = self.activation(T)
         m = ops.mix(T, mask, self.z_ratio, ACT_NONE if code is None else code)
-        a = ops.spmm(self.adj, m)
-        g = self.gn(a, p_drop=p, call_id=self.call_base)
+        a = agg(m)
+        g = self.gn(a, batch=batch, p_drop=p, call_id=self.call_base)
         c = torch.cat((g, x_), dim=-1)
-        C = ops.stacked_linear(c, self.comb_fns[1], self.comb_fns[0], stack.get("comb"))
+        C = ops.stacked_linear(c, self.comb_fns[1], self.comb_fns[0], stack.get("comb"), **rep)
         return ops.mix(C, mask, self.z_ratio, ACT_NONE)
 
 
@@ -220,6 +231,7 @@ class EmbZGConv(nn.Module):
             self.convs.append(layer)
         self.activation = activation
         self.dropout = dropout
+        self.replica_chunk = None  # exact zero-one labels (z [B, N]): replicas per group of launches; None = all B at once
         if gn:
             self.gns = nn.ModuleList([GraphNorm(hidden_channels) for _ in range(num_layers - 1)])
             self.gns.append(GraphNorm(output_channels + (num_layers - 1) * hidden_channels if jk else output_channels))
@@ -261,6 +273,10 @@ class EmbZGConv(nn.Module):
             x_flat = x_flat.to(torch.int64)
         if not x_flat.is_contiguous():  # a channel slice of a [N, C, 1] feature tensor: the kernels read a dense int64[N]
             x_flat = x_flat.contiguous()
+        if z is not None and z.dim() == 2 and z.shape[0] > 1 and z.shape[1] == n:
+            # exact zero-one labels (utils.ZeroOneZ): row b of z marks subgraph b alone -> [B, N, C], one replica of the graph
+            # per subgraph.  Always the per-op form (the stack program is one graph with one label vector).
+            return self._forward_replicas(x_flat, z, edge_index, edge_weight)
         if z is not None:
             # reference: mask = (z > 0.5) for whatever z holds (impl/models.py:243-248); the kernels read int64
             if z.numel() != n:
@@ -282,14 +298,59 @@ class EmbZGConv(nn.Module):
                 return self._forward_per_op(x_flat, z, edge_index, edge_weight, p)
         return self._forward_per_op(x_flat, z, edge_index, edge_weight, p)
 
-    def _forward_per_op(self, x_flat, z, edge_index, edge_weight, p):
+    def _forward_replicas(self, x_flat, z, edge_index, edge_weight):
+        """z [B, N] -> [B, N, C]: output row b is what z[b] alone gives on the whole graph (message passing, every GraphNorm
+        statistic).  The replicas run in groups of at most `replica_chunk`.  They are independent, their dropout key carries
+        the replica's index in the batch, and a training pass collects every parameter gradient replica by replica in an
+        ops.RepSink that is summed once, in an order that depends on B alone — so neither logits nor gradients depend on the
+        grouping, bit for bit.  (The dropout generator hashes the low 32 bits of the key: all replicas draw the same mask.)"""
+        B, n = z.shape
+        ops._need_gpu(x_flat, z, self.input_emb.weight)
+        if z.dtype == torch.uint8:  # label bytes as ops.zeroone_labels makes them: taken as they are
+            mask = z.contiguous()
+        else:
+            mask = (z > 0.5 if z.dtype != torch.int64 else z != 0).to(torch.uint8).contiguous()  # (impl/models.py:243-248: z > 0.5)
+        chunk = B if self.replica_chunk is None else int(self.replica_chunk)
+        if chunk < 1:
+            raise ValueError(f"EmbZGConv.replica_chunk must be None or >= 1, got {self.replica_chunk!r}")
+        p = self.dropout if self.training else 0.0
+        draws = self.training and (p > 0 or any(c.dropout > 0 for c in self.convs))
+        if draws:
+            ops.rng_advance(x_flat.device)  # new dropout masks for this forward/backward pair (one advance for all groups)
+        words = ops.rng_snapshot(x_flat.device) if (draws and torch.is_grad_enabled()) else None
+        outs = []
+        with ops.rng_scope(x_flat.device, words):
+            # the embedding and its GraphNorm do not see the labels: once on N rows, then replicated.  (Every replica's
+            # dropout mask of emb_gn is the one the plain call draws: the generator hashes the low 32 bits of the key.)
+            h0, _m = ops.embed_label(self.input_emb.weight, x_flat, None, self._selection(x_flat))
+            h0 = self.emb_gn(h0, p_drop=p, call_id=1)
+            sink = None
+            if torch.is_grad_enabled() and any(t.requires_grad for t in self.parameters()):
+                sink = ops.RepSink(B, h0.device)
+                h0 = ops.replica_root(h0, sink)
+            for rep0 in range(0, B, chunk):
+                rep = ops.Replicas(min(chunk, B - rep0), n, rep0, sink)
+                m = mask[rep0:rep0 + rep.R].reshape(-1)
+                if m.data_ptr() % 16:  # (a group that starts inside the batch: the dense kernels read the bytes in pairs)
+                    m = m.clone()
+                out = self._forward_per_op(x_flat, None, edge_index, edge_weight, p, rep=rep, h0=h0, mask=m)
+                outs.append(out.view(rep.R, n, out.shape[1]))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+    def _forward_per_op(self, x_flat, z, edge_index, edge_weight, p, rep=None, h0=None, mask=None):
+        """rep (an ops.Replicas) with h0 (the embedded, normalised rows [N, H]) and mask (uint8 [R * N]): the replicated form."""
         n = x_flat.shape[0]
         arena = getattr(self, "_glass_arena", None)
         if arena is not None:
             arena.refresh_transposes()  # operand images (W, W^T) of the fused dense kernels follow the weights
         code = _act_code(self.activation)
-        h, mask = ops.embed_label(self.input_emb.weight, x_flat, z, self._selection(x_flat))
-        h = self.emb_gn(h, p_drop=p, call_id=1)
+        if rep is None:
+            h, mask = ops.embed_label(self.input_emb.weight, x_flat, z, self._selection(x_flat))
+            h = self.emb_gn(h, p_drop=p, call_id=1)
+        else:
+            n = rep.R * rep.N
+            h = ops.replicate_rows(h0, rep)
+        extra = {} if rep is None else {"batch": rep}
         xs = []
         # JK buffer written in place by the fused layers (no torch.cat) when every layer takes that path
         widths = [c.trans_fns[0].weight.shape[0] for c in self.convs if isinstance(c, GLASSConv)]
@@ -301,17 +362,17 @@ class EmbZGConv(nn.Module):
             jk_buf = torch.empty((n, sum(widths)), dtype=torch.float32, device=h.device)
         for layer, conv in enumerate(self.convs):
             if jk_buf is not None:
-                h = conv(h, edge_index, edge_weight, mask, out=jk_buf[:, layer * widths[0]:(layer + 1) * widths[0]])
+                h = conv(h, edge_index, edge_weight, mask, out=jk_buf[:, layer * widths[0]:(layer + 1) * widths[0]], **extra)
             else:
-                h = conv(h, edge_index, edge_weight, mask)
+                h = conv(h, edge_index, edge_weight, mask, **extra)
             xs.append(h)
             if layer + 1 == len(self.convs):
                 break
             if self.gns is not None:
                 if code is not None:
-                    h = self.gns[layer](h, act=code, p_drop=p, call_id=conv.call_base + 1)
+                    h = self.gns[layer](h, act=code, p_drop=p, call_id=conv.call_base + 1, **extra)
                     continue
-                h = self.gns[layer](h)
+                h = self.gns[layer](h, **extra)
             h = self.activation(h)
             h = F.dropout(h, p=self.dropout, training=self.training)
         if jk_buf is not None:
@@ -319,7 +380,7 @@ class EmbZGConv(nn.Module):
         else:
             h = torch.cat(xs, dim=-1) if self.jk else xs[-1]
         if self.gns is not None:
-            h = self.gns[-1](h)
+            h = self.gns[-1](h, **extra)
         return h
 
 
@@ -417,6 +478,15 @@ class GLASS(nn.Module):
         return torch.stack(embs, dim=1).mean(dim=1)
 
     def Pool(self, emb, subG_node, pool):
+        if emb.dim() == 3:
+            # exact zero-one labels: emb [B, N, C] holds one replica of the graph per subgraph; row b of subG_node pools from
+            # replica b only — the existing pools on the flattened matrix, the valid entries moved to their replica's rows
+            B, N, C = emb.shape
+            if subG_node.shape[0] != B:
+                raise ValueError(f"Pool: {subG_node.shape[0]} subgraphs for {B} replicas")
+            shift = torch.arange(B, dtype=subG_node.dtype, device=subG_node.device).unsqueeze(1) * N
+            valid = (subG_node >= 0) & (subG_node < N)
+            return self.Pool(emb.reshape(B * N, C), torch.where(valid, subG_node + shift, torch.full_like(subG_node, -1)), pool)
         if isinstance(pool, AttnPool) and pool.trans_fn is None:
             return ops.attn_pool(emb, subG_node, pool.gate.weight)
         if isinstance(pool, PoolModule) and pool.trans_fn is None and pool.mode is not None:

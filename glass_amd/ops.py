@@ -344,7 +344,7 @@ class StackedLinearFn(torch.autograd.Function):
     (rocBLAS/hipBLASLt through torch).  With a ParamArena the stacked weight is a view (no cat) and
     the backward accumulates dW / db straight into the gradient arena with the split-K MFMA kernel."""
     @staticmethod
-    def forward(ctx, x, w1, w0, b1, b0, stack):
+    def forward(ctx, x, w1, w0, b1, b0, stack, rep=None):
         _need_gpu(x, w1)
         if stack is not None:
             W, b = stack[0], stack[1]
@@ -352,6 +352,7 @@ class StackedLinearFn(torch.autograd.Function):
             W, b = torch.cat((w1, w0)), torch.cat((b1, b0))
         ctx.save_for_backward(x, W)
         ctx.stack = stack
+        ctx.rep = rep if (rep is not None and rep.sink is not None) else None
         ctx.params = (w1, w0, b1, b0)
         ctx.split = w1.shape[0]
         return torch.addmm(b, x, W.t())
@@ -362,22 +363,40 @@ class StackedLinearFn(torch.autograd.Function):
         dT, _ = _rows(dT)
         if ctx.stack is not None and not _arena_grads_live(ctx.stack, ctx.params):
             ctx.stack = None  # .grad no longer aliases the arena: gradients go back through autograd
-        dx = torch.mm(dT, W) if ctx.needs_input_grad[0] else None
+        dx = torch.mm(dT, W) if (ctx.needs_input_grad[0] and ctx.rep is None) else (None if not ctx.needs_input_grad[0] else dT)
+        if ctx.rep is not None:
+            # replicas: every replica's weight gradient on its own, into its slot of the sink (summed over the replicas in a
+            # fixed order when the whole batch is through: RepSink.fold) — the bits do not depend on the grouping
+            rep, N = ctx.rep, ctx.rep.N
+            Ws, bs = rep.sink.linear(ctx.params, W.shape)
+            if dx is not None:
+                # (the library GEMM picks its kernel by the row count: one product per replica, N rows whatever the group)
+                dx = torch.empty((dT.shape[0], W.shape[1]), dtype=dT.dtype, device=dT.device)
+            for r in range(rep.R):
+                g, xr = dT[r * N:(r + 1) * N], x[r * N:(r + 1) * N]
+                if dx is not None:
+                    torch.mm(g, W, out=dx[r * N:(r + 1) * N])
+                dWr, dbr = Ws[rep.rep0 + r], bs[rep.rep0 + r]
+                if not linear_wgrad(g, xr, dWr, dbr, False):
+                    g, xr = g.clone(), xr.clone()  # (fresh, equally aligned operands whatever the group's base address)
+                    torch.mm(g.t(), xr, out=dWr)
+                    torch.sum(g, 0, out=dbr)
+            return dx, None, None, None, None, None, None
         if ctx.stack is not None and _wgrad_supported(dT, x, ctx.stack[2]) and ctx.stack[2].is_contiguous():
             # arena views: dW / db accumulate straight into the gradient arena (no temporaries, no autograd add kernels)
             if linear_wgrad(dT, x, ctx.stack[2], ctx.stack[3], True):
-                return dx, None, None, None, None, None
+                return dx, None, None, None, None, None, None
         dW = torch.empty_like(W)
         db = torch.empty(W.shape[0], dtype=W.dtype, device=W.device)
         if not linear_wgrad(dT, x, dW, db, False):
             dW = torch.mm(dT.t(), x)
             db = dT.sum(0)
         k = ctx.split
-        return dx, dW[:k], dW[k:], db[:k], db[k:], None
+        return dx, dW[:k], dW[k:], db[:k], db[k:], None, None
 
 
-def stacked_linear(x, lin1, lin0, stack=None):
-    return StackedLinearFn.apply(x, lin1.weight, lin0.weight, lin1.bias, lin0.bias, stack)
+def stacked_linear(x, lin1, lin0, stack=None, rep=None):
+    return StackedLinearFn.apply(x, lin1.weight, lin0.weight, lin1.bias, lin0.bias, stack, rep)
 
 
 class JoinColsFn(torch.autograd.Function):
@@ -424,7 +443,8 @@ class DualLinearMixFn(torch.autograd.Function):
     gradients are accumulated straight into the gradient arena (stack = arena views W, b, dW, db + the packed
     operand images of W and W^T)."""
     @staticmethod
-    def forward(ctx, xa, xb, w1, w0, b1, b0, mask, z_ratio, act, stack, out):
+    def forward(ctx, xa, xb, w1, w0, b1, b0, mask, z_ratio, act, stack, out, rep=None):
+        ctx.rep = rep if (rep is not None and rep.sink is not None) else None
         _need_gpu(xa, mask)
         xa, lda = _rows(xa)
         n, H = xa.shape
@@ -462,6 +482,24 @@ class DualLinearMixFn(torch.autograd.Function):
             _lib.check(rc, "glass_dual_linear_dgrad_f32")
         I = n_out
         ws = _wgrad_workspace(dout.device, n, 2 * H, I)
+        da = din if xb is None else (None if din is None else din[:, :H])
+        db_ = None if (xb is None or din is None) else din[:, H:]
+        if ctx.rep is not None:
+            # replicas: one weight-gradient launch per replica into its slot of the sink (see StackedLinearFn.backward)
+            rep, N = ctx.rep, ctx.rep.N
+            Ws, bs = rep.sink.linear(ctx.params, (2 * H, I))
+            for r in range(rep.R):
+                mk = mask[r * N:(r + 1) * N]
+                if mk.data_ptr() % 16:
+                    mk = mk.clone()
+                dWr, dbr = Ws[rep.rep0 + r], bs[rep.rep0 + r]
+                rc = lib.glass_dual_linear_wgrad_f32(dout[r * N:].data_ptr(), ldd, 0 if T is None else T[r * N:].data_ptr(), ldt,
+                                                     mk.data_ptr(), z_ratio, act_word(act), xa[r * N:].data_ptr(), xa.stride(0),
+                                                     0 if xb is None else xb[r * N:].data_ptr(),
+                                                     0 if xb is None else xb.stride(0), N, H, dWr.data_ptr(), dWr.stride(0),
+                                                     dbr.data_ptr(), 0, ws.data_ptr(), _stream())
+                _lib.check(rc, "glass_dual_linear_wgrad_f32")
+            return da, db_, None, None, None, None, None, None, None, None, None, None
         live = _arena_grads_live(stack, ctx.params)
         if live:   # accumulate straight into the gradient arena
             dW, dbias, accumulate = stack[2], stack[3], 1
@@ -474,15 +512,13 @@ class DualLinearMixFn(torch.autograd.Function):
                                              0 if xb is None else xb.stride(0), n, H, dW.data_ptr(),
                                              dW.stride(0), dbias.data_ptr(), accumulate, ws.data_ptr(), _stream())
         _lib.check(rc, "glass_dual_linear_wgrad_f32")
-        da = din if xb is None else (None if din is None else din[:, :H])
-        db_ = None if (xb is None or din is None) else din[:, H:]
         if live:
-            return da, db_, None, None, None, None, None, None, None, None, None
-        return da, db_, dW[:H], dW[H:], dbias[:H], dbias[H:], None, None, None, None, None
+            return da, db_, None, None, None, None, None, None, None, None, None, None
+        return da, db_, dW[:H], dW[H:], dbias[:H], dbias[H:], None, None, None, None, None, None
 
 
-def dual_linear_mix(xa, xb, lin1, lin0, mask, z_ratio, act, stack, out=None):
-    return DualLinearMixFn.apply(xa, xb, lin1.weight, lin0.weight, lin1.bias, lin0.bias, mask, z_ratio, act, stack, out)
+def dual_linear_mix(xa, xb, lin1, lin0, mask, z_ratio, act, stack, out=None, rep=None):
+    return DualLinearMixFn.apply(xa, xb, lin1.weight, lin0.weight, lin1.bias, lin0.bias, mask, z_ratio, act, stack, out, rep)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -789,3 +825,239 @@ def attn_pool(emb, pos, weight, return_alpha=False):
     ([C] or [1, C], no bias): [B, C] — and the attention weights [B, Smax] (no gradient) with return_alpha."""
     out, alpha = AttnPoolFn.apply(emb, pos, weight)
     return (out, alpha) if return_alpha else out
+
+
+# ---------------------------------------------------------------------------------------------
+# K4r / K1r / K6r  exact zero-one labels: R replicas of one graph, replica-major rows (row r * N + n)
+# ---------------------------------------------------------------------------------------------
+class Replicas:
+    """Marks an activation matrix [R * N, C] as R replicas of one N-node graph, the replicas rep0 .. rep0 + R - 1 of a batch.
+    rep0 enters the dropout key (call_id + ((rep0 + r) << 32): the replica's index in the WHOLE batch, so the key does not
+    depend on how the batch is cut into groups; the generator hashes the low 32 bits of call_id only, so today all replicas
+    of a call draw the SAME mask) and names the replica's slot in `sink`.  Passed as `batch` to models.GraphNorm and
+    models.GLASSConv."""
+    def __init__(self, R, N, rep0=0, sink=None):
+        self.R, self.N, self.rep0 = int(R), int(N), int(rep0)
+        self.sink = sink  # a RepSink: where the backward of a training pass over a whole batch collects parameter gradients
+        if self.R < 1 or self.N < 1 or self.rep0 < 0:
+            raise ValueError(f"Replicas: need R >= 1, N >= 1, rep0 >= 0 (got {R}, {N}, {rep0})")
+
+    def __repr__(self):
+        return f"Replicas(R={self.R}, N={self.N}, rep0={self.rep0})"
+
+
+class RepSink:
+    """Parameter gradients of ONE training pass over B replicas (EmbZGConv with z [B, N]).  The backward of every replica-form
+    op writes each replica's own contribution into slot rep0 + r of a [B, ...] buffer — one weight-gradient launch per
+    replica, GraphNorm's per-replica fp64 terms, the gradient of the replicated input rows — and `fold`, run by
+    ReplicaRootFn's backward once every group is through, sums the slots over the replicas and adds the sums to the
+    parameters' .grad.  Slot shapes and the sum's order depend on B only: the gradient bits do not depend on how the batch was
+    cut into groups (EmbZGConv.replica_chunk), nor on the order in which autograd ran the groups."""
+    def __init__(self, B, device):
+        self.B, self.device = int(B), device
+        self._lin, self._gn, self.rows = {}, {}, None
+
+    def linear(self, params, wshape):
+        """([B, 2O, I], [B, 2O]) slots of a Linear pair (params = w1, w0, b1, b0; stacked [W1; W0])."""
+        hit = self._lin.get(id(params[0]))
+        if hit is None:
+            hit = self._lin[id(params[0])] = (params, torch.zeros((self.B, ) + tuple(wshape), dtype=torch.float32, device=self.device),
+                                              torch.zeros((self.B, wshape[0]), dtype=torch.float32, device=self.device))
+        return hit[1], hit[2]
+
+    def graphnorm(self, params, C):
+        """[B, 3, C] fp64 slots (sum g * xhat, sum g, dalpha) of a GraphNorm (params = gamma, beta, alpha)."""
+        hit = self._gn.get(id(params[0]))
+        if hit is None:
+            hit = self._gn[id(params[0])] = (params, torch.zeros((self.B, 3, C), dtype=torch.float64, device=self.device))
+        return hit[1]
+
+    def input_rows(self, N, H):
+        if self.rows is None:
+            self.rows = torch.zeros((self.B, N, H), dtype=torch.float32, device=self.device)
+        return self.rows
+
+    @staticmethod
+    def _add(p, g):
+        if p.requires_grad:
+            if p.grad is None:
+                p.grad = g.reshape(p.shape).clone()
+            else:
+                p.grad.add_(g.reshape(p.shape))
+
+    def fold(self):
+        """Sum every slot buffer over the replicas into the parameters' .grad; returns the input rows' gradient [N, H]."""
+        for (w1, w0, b1, b0), Ws, bs in self._lin.values():
+            dW, db = Ws.sum(0), bs.sum(0)
+            k = w1.shape[0]
+            self._add(w1, dW[:k]), self._add(w0, dW[k:]), self._add(b1, db[:k]), self._add(b0, db[k:])
+        for (gamma, beta, alpha), S in self._gn.values():
+            s = S.sum(0).to(torch.float32)
+            self._add(gamma, s[0]), self._add(beta, s[1]), self._add(alpha, s[2])
+        return None if self.rows is None else self.rows.sum(0)
+
+
+class ReplicaRootFn(torch.autograd.Function):
+    """Identity on the rows every group of replicas starts from; its backward runs when all groups are through (each depends
+    on it) and folds the sink: parameter gradients into .grad, the rows' gradient to autograd."""
+    @staticmethod
+    def forward(ctx, h, anchor, sink):
+        ctx.sink = sink
+        return h.view_as(h)
+
+    @staticmethod
+    def backward(ctx, _g):
+        return ctx.sink.fold(), None, None
+
+
+class ReplicateRowsFn(torch.autograd.Function):
+    """[N, H] -> [R * N, H], the rows repeated for each replica; the backward puts each replica's gradient into its slot of the
+    sink (summed by RepSink.fold) and hands autograd zeros."""
+    @staticmethod
+    def forward(ctx, h, rep):
+        ctx.rep = rep
+        return h.unsqueeze(0).expand(rep.R, *h.shape).reshape(rep.R * h.shape[0], h.shape[1])
+
+    @staticmethod
+    def backward(ctx, g):
+        rep = ctx.rep
+        N, H = g.shape[0] // rep.R, g.shape[1]
+        rep.sink.input_rows(N, H)[rep.rep0:rep.rep0 + rep.R].copy_(g.reshape(rep.R, N, H))
+        return torch.zeros((N, H), dtype=g.dtype, device=g.device), None
+
+
+def replica_root(h, sink):
+    """(the anchor makes the node part of the graph even when nothing upstream of h requires a gradient)"""
+    return ReplicaRootFn.apply(h, torch.zeros((), device=h.device, requires_grad=True), sink)
+
+
+def replicate_rows(h, rep):
+    if rep.sink is None:
+        return h.unsqueeze(0).expand(rep.R, *h.shape).reshape(rep.R * h.shape[0], h.shape[1])
+    return ReplicateRowsFn.apply(h, rep)
+
+
+def _chunk_error(lib, what):
+    msg = lib.glass_last_error_string().decode(errors="replace")
+    return GlassHipError(f"{what}: {msg}; run the replicas in smaller groups (EmbZGConv.replica_chunk)")
+
+
+def zeroone_labels(pos, n_nodes, rep0=0, R=None):
+    """Label bytes uint8 [R * n_nodes] of the rows rep0 .. rep0 + R - 1 of the padded node matrix pos [B, Smax]: byte
+    r * n_nodes + n is 1 iff node n occurs in row rep0 + r (-1 and ids >= n_nodes are skipped).  One launch."""
+    _need_gpu(pos)
+    if pos.dim() != 2:
+        raise GlassHipError(f"zeroone_labels: pos must be [B, Smax], got {tuple(pos.shape)}")
+    pos = pos.contiguous()
+    if pos.dtype != torch.int64:
+        pos = pos.to(torch.int64)
+    B, Smax = pos.shape
+    R = B - int(rep0) if R is None else int(R)
+    mask = torch.empty(max(R, 0) * int(n_nodes), dtype=torch.uint8, device=pos.device)
+    _lib.check(_lib.load().glass_zeroone_labels_u8(pos.data_ptr(), B, Smax, int(rep0), R, int(n_nodes), mask.data_ptr(), _stream()),
+               "glass_zeroone_labels_u8")
+    return mask
+
+
+class SpMMRepFn(torch.autograd.Function):
+    """y[r] = A @ x[r] for R replicas in one launch (replica-major rows); backward dx[r] = A^T @ dy[r], the same entry on
+    the CSR of A^T.  Replica r has the bits SpMMFn gives on its slice."""
+    @staticmethod
+    def forward(ctx, adj, x, R):
+        _need_gpu(x)
+        x, _ = _rows(x)
+        ctx.adj, ctx.R = adj, R
+        return adj.fwd.spmm_rep(x, R)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy, _ = _rows(dy)
+        return None, ctx.adj.bwd.spmm_rep(dy, ctx.R), None
+
+
+def spmm_rep(adj, x, R):
+    return SpMMRepFn.apply(adj, x, int(R))
+
+
+class GraphNormRepFn(torch.autograd.Function):
+    """y = dropout(act(GraphNorm(x))) with x [R * N, C] as R graphs of N rows, each normalised over its own rows; the shared
+    parameters receive the sum of the replicas' gradients.  Replica r has the bits GraphNormFn gives on its slice with the
+    dropout stream call_id + ((rep0 + r) << 32)."""
+    @staticmethod
+    def forward(ctx, x, gamma, beta, alpha, eps, act, p_drop, call_id, rep, direct=False):
+        _need_gpu(x, gamma)
+        x, ldx = _rows(x)
+        n, C = x.shape
+        R, N = rep.R, rep.N
+        if n != R * N:
+            raise GlassHipError(f"graphnorm_rep: {n} rows for {rep!r}")
+        lib = _lib.load()
+        y = torch.empty((n, C), dtype=torch.float32, device=x.device)
+        saved = torch.empty(R * 4 * C, dtype=torch.float32, device=x.device)
+        from . import graph as ggraph
+        ws = _scratch(("graphnorm_rep", C, ggraph._ws_branch), x.device, lib.glass_graphnorm_rep_ws_bytes(N, C, R))
+        words = rng_tensor(x.device) if p_drop > 0 else None  # this pass's (seed, step): the backward re-reads THESE
+        rng = words.data_ptr() if words is not None else 0
+        g, b, a = gamma.contiguous(), beta.contiguous(), alpha.contiguous()
+        rc = lib.glass_graphnorm_rep_fwd_f32(x.data_ptr(), ldx, y.data_ptr(), C, N, C, R, rep.rep0, g.data_ptr(), b.data_ptr(),
+                                             a.data_ptr(), eps, saved.data_ptr(), act, p_drop, rng, call_id, ws.data_ptr(),
+                                             _stream())
+        if rc == -3:
+            raise _chunk_error(lib, "glass_graphnorm_rep_fwd_f32")
+        _lib.check(rc, "glass_graphnorm_rep_fwd_f32")
+        ctx.save_for_backward(x, g, a, saved)
+        ctx.cfg = (act, p_drop, call_id, rep)
+        ctx.sink_params = (gamma, beta, alpha) if rep.sink is not None else None
+        ctx.rng_words = words
+        ctx.rng_epoch = rng_epoch(x.device)
+        # direct: parameter gradients are accumulated straight into the flat gradient arena
+        ctx.direct = (gamma, beta, alpha) if (direct and all(t.grad is not None for t in (gamma, beta, alpha))) else None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, g, a, saved = ctx.saved_tensors
+        act, p_drop, call_id, rep = ctx.cfg
+        n, C = x.shape
+        dy, lddy = _rows(dy)
+        dx = torch.empty((n, C), dtype=torch.float32, device=x.device)
+        sink = rep.sink if ctx.sink_params is not None else None
+        if sink is not None:
+            dg = db = da = None  # the per-replica terms go to the sink (below); no fold in this launch
+            accumulate = 0
+        elif ctx.direct is not None:
+            dg, db, da = (t.grad for t in ctx.direct)
+            accumulate = 1
+        else:
+            dparams = torch.empty((3, C), dtype=torch.float32, device=x.device)
+            dg, db, da = dparams[0], dparams[1], dparams[2]
+            accumulate = 0
+        lib = _lib.load()
+        from . import graph as ggraph
+        ws = _scratch(("graphnorm_rep", C, ggraph._ws_branch), x.device, lib.glass_graphnorm_rep_ws_bytes(rep.N, C, rep.R))
+        if p_drop > 0 and ctx.rng_words is rng_state(x.device):  # no snapshot was taken: the live words must be unchanged
+            check_rng_epoch(x.device, ctx.rng_epoch, "GraphNormRepFn.backward")
+        rng = ctx.rng_words.data_ptr() if p_drop > 0 else 0
+        ldx = x.stride(0) if n > 1 else max(C, x.stride(0))
+        rc = lib.glass_graphnorm_rep_bwd_f32(dy.data_ptr(), lddy, x.data_ptr(), ldx, dx.data_ptr(), C, 0, 0, rep.N, C, rep.R,
+                                             rep.rep0, g.data_ptr(), a.data_ptr(), saved.data_ptr(),
+                                             0 if dg is None else dg.data_ptr(), 0 if db is None else db.data_ptr(),
+                                             0 if da is None else da.data_ptr(), accumulate, act, p_drop, rng, call_id,
+                                             ws.data_ptr(), _stream())
+        _lib.check(rc, "glass_graphnorm_rep_bwd_f32")
+        if sink is not None:
+            # the replicas' fp64 terms [R, 3, C] lie behind the R per-replica chunks of ws (include/glass_hip.h)
+            off = rep.R * lib.glass_graphnorm_ws_bytes(rep.N, C)
+            terms = ws[off:off + rep.R * 3 * C * 8].view(torch.float64).view(rep.R, 3, C)
+            sink.graphnorm(ctx.sink_params, C)[rep.rep0:rep.rep0 + rep.R].copy_(terms)
+            return dx, None, None, None, None, None, None, None, None, None
+        if ctx.direct is not None:
+            return dx, None, None, None, None, None, None, None, None, None
+        return dx, dg, db, da, None, None, None, None, None, None
+
+
+def graphnorm_rep(x, rep, gamma, beta, alpha, eps=1e-5, act=ACT_NONE, p_drop=0.0, call_id=0, direct=False):
+    """GraphNorm over the R replicas `rep` (an ops.Replicas) of one graph, each over its own N rows."""
+    if not isinstance(rep, Replicas):
+        raise GlassHipError(f"graphnorm_rep: rep must be an ops.Replicas, got {type(rep).__name__}")
+    return GraphNormRepFn.apply(x, gamma, beta, alpha, float(eps), int(act), float(p_drop), int(call_id), rep, bool(direct))

@@ -38,13 +38,16 @@ _VERIFY_TOL = 1e-5
 
 class TrainStep:
     def __init__(self, model, optimizer, loss_fn, x, edge_index, edge_weight, bucket=None, use_graph=True,
-                 warmup_iters=3, preserve_state=False):
+                 warmup_iters=3, preserve_state=False, z_fn=None):
         """preserve_state: the warm-up steps are run for their side effects only (CSR / plan / workspace / BLAS
         handle creation) and parameters, optimizer state and dropout stream are restored afterwards, so the
         training trajectory is exactly the one of a loop without warm-up (used by impl.train.train)."""
         from . import losses
         self.model, self.opt, self.loss_fn = model, optimizer, losses.on_device(loss_fn, x.device)  # (a marker's weights: on the GPU)
         self.x, self.ei, self.ew = x, edge_index, edge_weight
+        # how a batch is labeled: utils.MaxZOZ (the default; the step program labels from pos itself) or utils.ZeroOneZ (exact
+        # labels, one replica of the graph per subgraph: always the per-op autograd step, captured like any other)
+        self.z_fn = utils.MaxZOZ if z_fn is None else z_fn
         self.bucket = bucket if bucket is not None else gdist.bucket_for(model)
         self.use_graph = use_graph
         self.warmup_iters = warmup_iters
@@ -103,7 +106,7 @@ class TrainStep:
     def _program_step(self):
         from . import stack
         # (the step program's fused readout holds the bare Linear head only: an MLP head runs the autograd form below)
-        return (self._fused_head() == "linear" and hasattr(self.bucket, "flat_param") and self.x.dim() == 3 and
+        return (self.z_fn is utils.MaxZOZ and self._fused_head() == "linear" and hasattr(self.bucket, "flat_param") and self.x.dim() == 3 and
                 self.x.shape[1:] == (1, 1) and stack.step_supported(self.model, self.loss_fn))
 
     def _fwd_bwd(self, tail_hook=None, apply_opt=False):
@@ -128,7 +131,7 @@ class TrainStep:
             return stack.applied_optimizer(self.model)
         if tail_hook is not None:
             raise RuntimeError("tail_hook needs the step program")
-        z = utils.MaxZOZ(self.x, self._pos)
+        z = self.z_fn(self.x, self._pos)
         self.bucket.zero()
         kind = self._fused_head()
         if kind is not None:

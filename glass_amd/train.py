@@ -14,7 +14,8 @@ USE_HEAD_LABELS = os.environ.get("GLASS_HEAD_LABELS", "1") != "0"  # 0: the labe
 
 def _graph_step(optimizer, model, dataloader, loss_fn):
     """The training step object (glass_amd.step.TrainStep: the step program, replayed from a hipGraph unless
-    GLASS_TRAIN_GRAPH=0) when the epoch is graph-safe: a GLASS model on the GPU, ZGDataloader with z_fn = MaxZOZ and
+    GLASS_TRAIN_GRAPH=0) when the epoch is graph-safe: a GLASS model on the GPU, ZGDataloader with z_fn = MaxZOZ (or ZeroOneZ:
+    the per-op step with exact labels) and
     drop_last (fixed batch shape), and an optimizer whose step is capturable — optim.FlatAdam, or a plain
     `torch.optim.Adam(model.parameters(), lr)` as the reference driver builds it (GLASSTest.py:213), which is taken over
     in place (optim.adopt: flat parameter arena built on the spot, the torch optimizer's param_groups / state stay the
@@ -25,7 +26,7 @@ def _graph_step(optimizer, model, dataloader, loss_fn):
     from .models import GLASS
     from .optim import FlatAdam, adopt, adoptable
     if not (USE_STEP and isinstance(model, GLASS) and isinstance(dataloader, ZGDataloader) and
-            dataloader.z_fn is utils.MaxZOZ and dataloader.drop_last and dataloader.Gdataset.x.is_cuda and
+            dataloader.z_fn in (utils.MaxZOZ, utils.ZeroOneZ) and dataloader.drop_last and dataloader.Gdataset.x.is_cuda and
             len(dataloader) > 0):
         return None
     engine = optimizer
@@ -38,13 +39,14 @@ def _graph_step(optimizer, model, dataloader, loss_fn):
     elif not optimizer.arena.attached():
         optimizer.arena.reattach()
     ds = dataloader.Gdataset
-    key = (id(optimizer), id(engine), id(loss_fn), id(ds.x), id(ds.edge_index), dataloader.batch_size, gdist.world_size(), USE_GRAPH)
+    key = (id(optimizer), id(engine), id(loss_fn), id(ds.x), id(ds.edge_index), dataloader.batch_size, gdist.world_size(), USE_GRAPH,
+           dataloader.z_fn)
     cache = model.__dict__.setdefault("_glass_train_steps", utils.RuntimeCache())
     step = cache.get(key)
     if step is None:
         from .step import TrainStep
         step = TrainStep(model, engine, loss_fn, ds.x, ds.edge_index, ds.edge_attr, gdist.bucket_for(model),
-                         use_graph=USE_GRAPH, warmup_iters=2, preserve_state=True)  # GLASS_TRAIN_GRAPH=0: the same step, eager launches
+                         use_graph=USE_GRAPH, warmup_iters=2, preserve_state=True, z_fn=dataloader.z_fn)  # GLASS_TRAIN_GRAPH=0: the same step, eager launches
         cache.clear()  # one live graph per model
         cache[key] = step
     return step

@@ -11,6 +11,25 @@ def MaxZOZ(x, pos):
     return ops.maxzoz(x.shape[0], pos)
 
 
+def ZeroOneZ(x, pos):
+    """Exact zero-one labeling trick: z[b, n] = 1 iff node n belongs to subgraph b — int64 [B, N], every subgraph of the
+    batch labeled on its own (MaxZOZ marks their union, so a subgraph's labels depend on its batch).  -1 padding and ids
+    >= N are skipped.  A model called with it returns what each subgraph gives alone (EmbZGConv: one replica of the graph
+    per subgraph, about B times the work and memory of a MaxZOZ batch).  On the GPU the label kernel
+    glass_zeroone_labels_u8; on the host (loaders over CPU data) a scatter."""
+    n = x.shape[0]
+    if pos.dim() != 2:
+        raise ValueError(f"ZeroOneZ: pos must be the padded [B, Smax] node matrix, got {tuple(pos.shape)}")
+    B = pos.shape[0]
+    if pos.is_cuda:
+        return ops.zeroone_labels(pos, n).view(B, n).to(torch.int64)
+    pos = pos.to(torch.int64)
+    z = torch.zeros((B, n + 1), dtype=torch.int64)
+    ok = (pos >= 0) & (pos < n)
+    z.scatter_(1, torch.where(ok, pos, torch.full_like(pos, n)), 1)
+    return z[:, :n].contiguous()
+
+
 def pad2batch(pad):
     """[[0,2,3],[1,4,5],[6,7,-1]] -> (batch=[0,0,0,1,1,1,2,2], pos=[0,2,3,1,4,5,6,7]): row-major
     flatten of the padded matrix with the -1 entries dropped."""

@@ -1051,6 +1051,58 @@ int glass_eval_auroc_supported(int64_t n, int64_t K);
 int glass_eval_auroc_counts_f32(const float* score, int64_t lds, const float* label, int64_t ldl, int64_t n, int64_t K,
                                 int64_t* counts, void* stream);
 
+/* ---- K4r / K1r / K6r  exact zero-one labels: R replicas of one graph (an extension) ---------------------------------------
+ * The reference's labeling (impl/utils.py:32-45, MaxZOZ) marks the UNION of a batch's subgraphs on one graph
+ * (impl/models.py:243-248), so a subgraph's logits depend on its batch.  Here every subgraph of a batch gets its own replica
+ * of the graph with only its own nodes marked: replica-major rows (activation row r * N + n, matrices [R * N, ld], label
+ * bytes uint8[R * N]), the same adjacency and parameters for every replica.  The dense kernels take R * N rows as they are;
+ * these entries are the pieces that need a form of their own.  All of them only enqueue on `stream`, keep no state, read no
+ * environment and no device memory on the host; argument errors come back as codes before any launch.
+ *
+ *   glass_zeroone_labels_u8: mask[r * n_nodes + n] = 1 iff node n occurs in row rep0 + r of pos [B, Smax] (-1 and ids >=
+ *     n_nodes are skipped), r < R, else 0.  One launch that zero-fills and marks (a workgroup owns a slab of the bytes);
+ *     a node named twice is harmless, nothing depends on the order.  GLASS_E_ARG: negative sizes, rows outside pos, null /
+ *     misaligned pointers; R * n_nodes == 0 is a valid no-op.
+ *
+ *   glass_spmm_csr_rep_f32: Y[r] = A @ X[r], r < R, in one launch (impl/models.py:164 per replica; with the CSR of A^T its
+ *     backward).  Same CSR, same plan blob as glass_spmm_csr_f32; X[r] starts x_rep_stride rows after X[r - 1], Y[r]
+ *     y_rep_stride (>= n_rows) rows after Y[r - 1]; the replica is the grid's z plane, so the plan and the indices exist
+ *     once in memory.  ws: glass_spmm_rep_ws_bytes(hdr, H, R) = R times the plan's partial rows.  Replica r's output has the
+ *     bits glass_spmm_csr_f32 gives on that replica's slice, for every plan form.  GLASS_E_UNSUPPORTED before any launch:
+ *     R > glass_spmm_rep_max_replicas() (the grid's z extent), or replicas that span more than 2^47 bytes.
+ *
+ *   glass_graphnorm_rep_fwd_f32 / _bwd_f32: GraphNorm (impl/models.py:165,249,257,266,271) over R segments of exactly
+ *     n_rows rows each, every segment over its own rows, with the row blocking, the fp64 partials in fixed order, the fused
+ *     activation and the fused inverted dropout of glass_graphnorm_fwd_f32 / _bwd_f32; saved = float[R * 4 * C].  Forward
+ *     and dx of replica r have the bits of those entries on the slice with call_id + ((uint64)(rep0 + r) << 32).  (The
+ *     generator hashes the low 32 bits of call_id: today the replicas of one call therefore draw the SAME mask, the one the
+ *     whole-graph entry draws for call_id itself.)  After _bwd_f32 the replicas' fp64 gradient terms double[R][3][C] =
+ *     (sum g * xhat, sum g, dalpha) lie in ws behind the R chunks of glass_graphnorm_ws_bytes(n_rows, C) bytes each.
+ *     dgamma / dbeta / dalpha (any may be NULL) are the sums over the replicas, folded from per-replica fp64 terms in
+ *     ascending r by a second small launch (no float atomics); `accumulate` as in the whole-graph entry.  ws:
+ *     glass_graphnorm_rep_ws_bytes(n_rows, C, R), 8-byte aligned.  R > glass_graphnorm_rep_max_replicas() ->
+ *     GLASS_E_UNSUPPORTED; R == 0 is a valid no-op (the backward then zero-fills the parameter gradients unless
+ *     `accumulate`).  glass_graphnorm_rep_row_block(C, vec): rows one statistics workgroup covers (vec: the 16-byte form). */
+int glass_zeroone_labels_u8(const int64_t* pos, int64_t B, int64_t Smax, int64_t rep0, int64_t R, int64_t n_nodes,
+                            uint8_t* mask, void* stream);
+int64_t glass_spmm_rep_max_replicas(void);
+int64_t glass_spmm_rep_ws_bytes(const int32_t* hdr, int64_t H, int64_t R);
+int glass_spmm_csr_rep_f32(const int32_t* rowptr, const int32_t* col, const float* val, const float* X, int64_t ldx,
+                           int64_t x_rep_stride, float* Y, int64_t ldy, int64_t y_rep_stride, int64_t n_rows, int64_t H,
+                           int64_t R, const int32_t* hdr, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_graphnorm_rep_max_replicas(void);
+int64_t glass_graphnorm_rep_row_block(int64_t C, int vec);
+int64_t glass_graphnorm_rep_ws_bytes(int64_t n_rows, int64_t C, int64_t R);
+int glass_graphnorm_rep_fwd_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t n_rows, int64_t C, int64_t R,
+                                int64_t rep0, const float* gamma, const float* beta, const float* alpha, float eps,
+                                float* saved, int act, float p_drop, const uint64_t* rng_state, uint64_t call_id, void* ws,
+                                void* stream);
+int glass_graphnorm_rep_bwd_f32(const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dx, int64_t lddx,
+                                const float* addend, int64_t ldadd, int64_t n_rows, int64_t C, int64_t R, int64_t rep0,
+                                const float* gamma, const float* alpha, const float* saved, float* dgamma, float* dbeta,
+                                float* dalpha, int accumulate, int act, float p_drop, const uint64_t* rng_state,
+                                uint64_t call_id, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
