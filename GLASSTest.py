@@ -52,6 +52,9 @@ def parse_args(argv=None):
                         "split's label counts, applied inside the fused loss (default: none)")
     p.add_argument("--pool", type=str, default=None, choices=tuple(POOLS),
                    help="(extension) readout instead of the config file's `pool` (default: the config's value)")
+    p.add_argument("--aggr", type=str, default=None, choices=("mean", "sum", "gcn", "max"),
+                   help="(extension) neighbour aggregation instead of the config file's `aggr` (default: the config's value); "
+                        "max: the largest weighted neighbour message per channel, not available with --use_zeroone")
     args = p.parse_args(argv)
     if args.use_zeroone and args.use_maxzeroone:
         p.error("--use_zeroone and --use_maxzeroone are mutually exclusive")
@@ -252,6 +255,8 @@ def main(argv=None):
     print("params", params, flush=True)
     if args.pool is not None:
         params["pool"] = args.pool
+    if args.aggr is not None:
+        params["aggr"] = args.aggr
     run.split()
     return run.test(**params)
 

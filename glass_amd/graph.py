@@ -9,6 +9,7 @@ HBM layout (all on the device the graph lives on):
   rowptr int32[N+1], col int32[nnz], val fp32[nnz]            CSR of A   (row = destination)
   rowptr_t, col_t, val_t                                      CSR of A^T (for the backward)
   plan / plan_t int32[...]                                    opaque K1 schedules
+  eid_t int32[nnz]                                            aggr "max" only: forward index of each entry of A^T
 Duplicate (row,col) entries are kept as separate entries: they add up in the product exactly as in
 the reference's uncoalesced COO matmul.
 """
@@ -128,9 +129,10 @@ def set_workspace_branch(b):
 
 
 class CSRAdj:
-    """Normalised adjacency A (forward) and A^T (backward) for one aggregation scheme."""
+    """Normalised adjacency A (forward) and A^T (backward) for one aggregation scheme.  aggr "max" (an extension): the raw
+    edge weights (the values of "sum"), aggregated by K1m (max_fwd / max_bwd) instead of K1's product."""
     def __init__(self, edge_index, edge_weight, n_node, aggr):
-        if aggr not in _lib.AGGR_MODES:
+        if aggr not in _lib.AGGR_MODES and aggr != "max":
             raise NotImplementedError  # same error type as the reference (models.py:110-111)
         if not edge_index.is_cuda:
             raise _lib.GlassHipError("glass_amd runs on the GPU only (edge_index is on %s); the CPU path lives in "
@@ -149,7 +151,7 @@ class CSRAdj:
         self.deg = torch.empty(n, dtype=torch.float32, device=dev)
         val = torch.empty(nnz, dtype=torch.float32, device=dev)
         rc = _lib.load().glass_adj_values_f32(rowptr.data_ptr(), col32.data_ptr(), w.data_ptr(), n,
-                                              _lib.AGGR_MODES[aggr], self.deg.data_ptr(), val.data_ptr(),
+                                              _lib.AGGR_MODES["sum" if aggr == "max" else aggr], self.deg.data_ptr(), val.data_ptr(),
                                               torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "glass_adj_values_f32")
         # transpose: same entries keyed by (col,row); values are permuted, never recomputed
@@ -160,10 +162,68 @@ class CSRAdj:
         self.n_node, self.aggr = n, aggr
         self.fwd = CSROperand(rowptr, col32, val, n, n)
         self.bwd = CSROperand(rowptr_t, col_t, val_t, n, n)
+        if aggr == "max":
+            self.eid_t = perm_t.to(torch.int32).contiguous()  # transposed entry t is forward entry eid_t[t]
+            self._max_ws = {}
+            self._retired_ws = []
 
     @property
     def nnz(self):
         return self.fwd.nnz
+
+    def _max_workspace(self, kind, H, nbytes):
+        """Partial rows of K1m's cut rows: one buffer per direction, feature width and branch (set_workspace_branch)."""
+        if nbytes < 0:
+            raise _lib.GlassHipError("bad plan header")
+        key = (kind, H, _ws_branch)
+        ws = self._max_ws.get(key)
+        if ws is None or ws.numel() * 4 < nbytes:
+            if ws is not None:
+                self._retired_ws.append(ws)  # (a captured graph may still launch with this pointer: never handed back)
+            ws = self._max_ws[key] = torch.empty(max(nbytes // 4, 4), dtype=torch.int32, device=self.fwd.rowptr.device)
+        return ws
+
+    def _need_max(self, what):
+        if self.aggr != "max":
+            raise _lib.GlassHipError(f"CSRAdj.{what}: this adjacency was built for aggr {self.aggr!r}, not 'max'")
+
+    def max_fwd(self, x):
+        """(y, arg) = K1m forward: y[i, c] = max over the entries e of row i of val[e] * x[col[e], c], arg the winning e
+        (int32; -1 and y = 0 for a row without entries)."""
+        self._need_max("max_fwd")
+        op = self.fwd
+        assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32 and x.is_cuda
+        assert x.shape[0] == op.n_cols, f"X has {x.shape[0]} rows, matrix has {op.n_cols} columns"
+        H = x.shape[1]
+        lib = _lib.load()
+        y = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
+        arg = torch.empty((op.n_rows, H), dtype=torch.int32, device=x.device)
+        ws = self._max_workspace("fwd", H, lib.glass_spmm_max_ws_bytes(op.header.ctypes.data, H))
+        ldx = x.stride(0) if x.shape[0] > 1 else max(H, x.stride(0))
+        rc = lib.glass_spmm_max_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
+                                        y.data_ptr(), H, arg.data_ptr(), H, op.n_rows, H, op.header.ctypes.data,
+                                        op.plan.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_max_csr_f32")
+        return y, arg
+
+    def max_bwd(self, dy, arg):
+        """dx of K1m: every dy[i, c] goes, times its entry's weight, to the source of the entry arg[i, c] names."""
+        self._need_max("max_bwd")
+        op = self.bwd
+        assert dy.dim() == 2 and dy.stride(1) == 1 and dy.dtype == torch.float32 and dy.is_cuda
+        assert arg.dtype == torch.int32 and arg.shape == dy.shape and arg.stride(1) == 1 and dy.shape[0] == op.n_cols
+        H = dy.shape[1]
+        lib = _lib.load()
+        dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=dy.device)
+        ws = self._max_workspace("bwd", H, lib.glass_spmm_max_bwd_ws_bytes(op.header.ctypes.data, H))
+        ldy = dy.stride(0) if dy.shape[0] > 1 else max(H, dy.stride(0))
+        lda = arg.stride(0) if arg.shape[0] > 1 else max(H, arg.stride(0))
+        rc = lib.glass_spmm_max_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
+                                        dy.data_ptr(), ldy, arg.data_ptr(), lda, dx.data_ptr(), H, op.n_rows, H,
+                                        op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
+                                        torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_max_bwd_f32")
+        return dx
 
     def to_dense(self):
         """Dense [N,N] (tests on tiny graphs only)."""

@@ -7,7 +7,7 @@ torch; there is no CPU path.
 Reference map (file:line under /root/reference):
   Seq 10-24 · MLP 27-80 · buildAdj 83-111 · GLASSConv 114-174 · EmbZGConv 177-272 ·
   PoolModule/AddPool/MaxPool/MeanPool/SizePool 275-319 · GLASS 322-355   (impl/models.py)
-Not in the reference: AttnPool (attention readout, pool "attn").
+Not in the reference: AttnPool (attention readout, pool "attn"); aggr "max" (max neighbour aggregation, buildAdj).
 """
 import torch
 import torch.nn as nn
@@ -142,8 +142,9 @@ _adj_cache = []  # [(edge_index, edge_weight, n, aggr, CSRAdj)] — tensors are 
 def buildAdj(edge_index, edge_weight, n_node: int, aggr: str):
     """Normalised adjacency for aggr in {mean,sum,gcn} as a device CSR (graph.CSRAdj) instead of the
     reference's COO.  One instance is shared by every layer asking for the same (graph, aggr) —
-    the reference builds an identical copy per layer (models.py:154-156)."""
-    if aggr not in ("mean", "sum", "gcn"):
+    the reference builds an identical copy per layer (models.py:154-156).  aggr "max" (an extension): the raw weights,
+    aggregated by ops.spmm with a max instead of a sum."""
+    if aggr not in ("mean", "sum", "gcn", "max"):
         raise NotImplementedError
     for ei, ew, n, a, adj in _adj_cache:
         if ei is edge_index and ew is edge_weight and n == int(n_node) and a == aggr:

@@ -164,7 +164,28 @@ class SpMMFn(torch.autograd.Function):
         return None, ctx.adj.bwd.spmm(dy)
 
 
+class SpMMMaxFn(torch.autograd.Function):
+    """y[i] = max over the entries of row i of A of val * x[col] (aggr "max", K1m: csrc/spmm_max.hip); the forward keeps
+    the winning entry of every output element, the backward routes dy through it (A carries no gradient)."""
+    @staticmethod
+    def forward(ctx, adj, x):
+        _need_gpu(x)
+        x, _ = _rows(x)
+        y, arg = adj.max_fwd(x)
+        ctx.adj = adj
+        ctx.save_for_backward(arg)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy, _ = _rows(dy)
+        (arg, ) = ctx.saved_tensors
+        return None, ctx.adj.max_bwd(dy, arg)
+
+
 def spmm(adj, x):
+    if getattr(adj, "aggr", None) == "max":
+        return SpMMMaxFn.apply(adj, x)
     return SpMMFn.apply(adj, x)
 
 
@@ -976,6 +997,9 @@ class SpMMRepFn(torch.autograd.Function):
 
 
 def spmm_rep(adj, x, R):
+    if getattr(adj, "aggr", None) == "max":
+        raise GlassHipError("replicated max aggregation is not built: aggr 'max' runs one graph at a time (no exact "
+                            "zero-one labels / --use_zeroone with it)")
     return SpMMRepFn.apply(adj, x, int(R))
 
 

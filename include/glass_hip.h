@@ -99,6 +99,38 @@ int glass_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* v
                        int64_t n_rows, int64_t H,
                        const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
 
+/* K1m max neighbour aggregation (aggr "max": an extension, the reference has none) at the call site K1 serves,
+ *     `self.adj @ x` (impl/models.py:164), on K1's CSR and plans.  Forward CSR of A: entries sorted by (row, col), stable,
+ *     duplicates kept as separate entries, row = destination; val = the raw edge weights (what aggr "sum" stores).
+ *
+ *   glass_spmm_max_csr_f32: Y[i,c] = max over entries e of row i of val[e] * X[col[e],c] — one fp32 multiply, rounded once —
+ *     and arg[i,c] = the winning e (an index into col / val).  Equal values (-0.0 == +0.0): the smallest e wins, as a scan
+ *     over e upward with `>` gives.  A row without entries: Y = 0, arg = -1 (torch_scatter's empty segment).  Y and arg are
+ *     functions of the inputs alone, bit for bit.  Inputs are finite; NaN is not part of the contract.
+ *     `plan` is glass_spmm_plan_build's for this row pointer; ws: glass_spmm_max_ws_bytes(hdr, H) = the plan's partial slots
+ *     times H (value, index) pairs.  Rows cut into chunks are combined by a second launch in slot order.
+ *   glass_spmm_max_bwd_f32: on the TRANSPOSED CSR (row j = source; col_t = destinations i_t; val_t; eid_t[t] = the index of
+ *     transposed entry t in the forward CSR; the transposed row pointer's plan):
+ *     dX[j,c] = sum over entries t of row j of (arg[i_t,c] == eid_t[t]) ? val_t[t] * dY[i_t,c] : 0, in a fixed order (lane-group
+ *     partial sums, cut rows from partial rows in chunk order: no float atomics, bitwise repeatable).  A carries no gradient.
+ *     ws: glass_spmm_max_bwd_ws_bytes(hdr_t, H).  Per entry it reads two [H] rows (arg and dY) where K1 reads one.
+ *   Both: every H and leading dimension K1 takes (16-byte vector form when H, the ld* and the pointers allow it, scalar form
+ *     otherwise).  Refused on the host before any launch: null or misaligned (4-byte) pointers, H <= 0, ld* < H -> GLASS_E_ARG;
+ *     a header that is no plan for n_rows -> GLASS_E_PLAN; H beyond 65535 * 64 columns -> GLASS_E_UNSUPPORTED.
+ *     The *_ws_bytes queries: GLASS_E_PLAN for a header that is no plan, GLASS_E_ARG for H <= 0. */
+int64_t glass_spmm_max_ws_bytes(const int32_t* plan_header_host, int64_t H);
+int glass_spmm_max_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val, /* CSR of A, device */
+                           const float* X, int64_t ldx,                                 /* [n_cols, H] */
+                           float* Y, int64_t ldy, int32_t* arg, int64_t ldarg,          /* [n_rows, H] each */
+                           int64_t n_rows, int64_t H,
+                           const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_spmm_max_bwd_ws_bytes(const int32_t* plan_t_header_host, int64_t H);
+int glass_spmm_max_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* val_t, const int32_t* eid_t, /* CSR of A^T */
+                           const float* dY, int64_t ldy, const int32_t* arg, int64_t ldarg,     /* [n_cols of A^T, H] each */
+                           float* dX, int64_t ldx,                                              /* [n_rows, H] */
+                           int64_t n_rows, int64_t H,
+                           const int32_t* plan_t_header_host, const int32_t* plan_t_dev, void* ws, void* stream);
+
 /* K2  normalised edge values of buildAdj (impl/models.py:83-111) on an (row,col)-sorted COO:
  *     deg = segment-sum of w per row, deg<0.5 -> +1; aggr 0=mean w/deg[row], 1=sum w,
  *     2=gcn deg[row]^-1/2 * w * deg[col]^-1/2.  Duplicate (row,col) entries stay separate CSR
