@@ -52,9 +52,11 @@ def parse_args(argv=None):
                         "split's label counts, applied inside the fused loss (default: none)")
     p.add_argument("--pool", type=str, default=None, choices=tuple(POOLS),
                    help="(extension) readout instead of the config file's `pool` (default: the config's value)")
-    p.add_argument("--aggr", type=str, default=None, choices=("mean", "sum", "gcn", "max"),
+    p.add_argument("--aggr", type=str, default=None, choices=("mean", "sum", "gcn", "max", "softmax"),
                    help="(extension) neighbour aggregation instead of the config file's `aggr` (default: the config's value); "
-                        "max: the largest weighted neighbour message per channel, not available with --use_zeroone")
+                        "max: the largest weighted neighbour message per channel; softmax: the softmax-weighted mean of the "
+                        "messages with a learned temperature per layer (positive edge weights); neither is available with "
+                        "--use_zeroone")
     args = p.parse_args(argv)
     if args.use_zeroone and args.use_maxzeroone:
         p.error("--use_zeroone and --use_maxzeroone are mutually exclusive")

@@ -76,6 +76,12 @@ SIGNATURES = {
     "glass_spmm_max_csr_f32": (c_int, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
     "glass_spmm_max_bwd_ws_bytes": (c_int64, [_P, _I]),
     "glass_spmm_max_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "glass_spmm_softmax_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_softmax_csr_f32": (c_int, [_P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "glass_spmm_softmax_bwd_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_softmax_bwd_f32": (c_int, [_P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "glass_spmm_softmax_dt_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_softmax_dt_f32": (c_int, [_P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
     "glass_adj_values_f32": (c_int, [_P, _P, _P, _I, c_int, _P, _P, _P]),
     "glass_maxzoz_i64": (c_int, [_P, _I, _P, _I, _P]),
     "glass_embed_label_f32": (c_int, [_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _P]),

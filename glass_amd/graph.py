@@ -10,6 +10,7 @@ HBM layout (all on the device the graph lives on):
   rowptr_t, col_t, val_t                                      CSR of A^T (for the backward)
   plan / plan_t int32[...]                                    opaque K1 schedules
   eid_t int32[nnz]                                            aggr "max" only: forward index of each entry of A^T
+aggr "max" and "softmax" keep the raw edge weights in val (the values of "sum"); "softmax" requires them > 0.
 Duplicate (row,col) entries are kept as separate entries: they add up in the product exactly as in
 the reference's uncoalesced COO matmul.
 """
@@ -130,9 +131,11 @@ def set_workspace_branch(b):
 
 class CSRAdj:
     """Normalised adjacency A (forward) and A^T (backward) for one aggregation scheme.  aggr "max" (an extension): the raw
-    edge weights (the values of "sum"), aggregated by K1m (max_fwd / max_bwd) instead of K1's product."""
+    edge weights (the values of "sum"), aggregated by K1m (max_fwd / max_bwd) instead of K1's product.  aggr "softmax" (an
+    extension): the raw weights too, strictly positive (checked here, once), aggregated by K1s (softmax_fwd / softmax_bwd /
+    softmax_dt) with a temperature the caller owns."""
     def __init__(self, edge_index, edge_weight, n_node, aggr):
-        if aggr not in _lib.AGGR_MODES and aggr != "max":
+        if aggr not in _lib.AGGR_MODES and aggr not in ("max", "softmax"):
             raise NotImplementedError  # same error type as the reference (models.py:110-111)
         if not edge_index.is_cuda:
             raise _lib.GlassHipError("glass_amd runs on the GPU only (edge_index is on %s); the CPU path lives in "
@@ -146,12 +149,15 @@ class CSRAdj:
         perm = torch.argsort(row * n + col, stable=True)
         row, col = row[perm], col[perm]
         w = edge_weight.to(torch.float32)[perm].contiguous()
+        if aggr == "softmax" and not bool((w > 0).all()):  # one device read; the kernels do not test it
+            raise ValueError("aggr 'softmax': edge weights are multiplicities and must be strictly positive")
         rowptr = _csr_from_sorted(row, n)
         col32 = col.to(torch.int32).contiguous()
         self.deg = torch.empty(n, dtype=torch.float32, device=dev)
         val = torch.empty(nnz, dtype=torch.float32, device=dev)
         rc = _lib.load().glass_adj_values_f32(rowptr.data_ptr(), col32.data_ptr(), w.data_ptr(), n,
-                                              _lib.AGGR_MODES["sum" if aggr == "max" else aggr], self.deg.data_ptr(), val.data_ptr(),
+                                              _lib.AGGR_MODES["sum" if aggr in ("max", "softmax") else aggr], self.deg.data_ptr(),
+                                              val.data_ptr(),
                                               torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "glass_adj_values_f32")
         # transpose: same entries keyed by (col,row); values are permuted, never recomputed
@@ -165,6 +171,9 @@ class CSRAdj:
         if aggr == "max":
             self.eid_t = perm_t.to(torch.int32).contiguous()  # transposed entry t is forward entry eid_t[t]
             self._max_ws = {}
+            self._retired_ws = []
+        if aggr == "softmax":
+            self._softmax_ws = {}
             self._retired_ws = []
 
     @property
@@ -224,6 +233,88 @@ class CSRAdj:
                                         torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "glass_spmm_max_bwd_f32")
         return dx
+
+    def _softmax_workspace(self, kind, H, nbytes):
+        """Workspaces of K1s: one buffer per entry ("fwd": partial triples, "bwd": partial rows, "dt": fp64 partials), feature
+        width and branch (set_workspace_branch)."""
+        if nbytes < 0:
+            raise _lib.GlassHipError("bad plan header")
+        key = (kind, H, _ws_branch)
+        ws = self._softmax_ws.get(key)
+        if ws is None or ws.numel() * 8 < nbytes:
+            if ws is not None:
+                self._retired_ws.append(ws)  # (a captured graph may still launch with this pointer: never handed back)
+            ws = self._softmax_ws[key] = torch.empty(max((nbytes + 7) // 8, 2), dtype=torch.float64, device=self.fwd.rowptr.device)
+        return ws
+
+    def _need_softmax(self, what):
+        if self.aggr != "softmax":
+            raise _lib.GlassHipError(f"CSRAdj.{what}: this adjacency was built for aggr {self.aggr!r}, not 'softmax'")
+
+    @staticmethod
+    def _softmax_operand(a, n, name):
+        assert a.dim() == 2 and a.stride(1) == 1 and a.dtype == torch.float32 and a.is_cuda, name
+        assert a.shape[0] == n, f"{name} has {a.shape[0]} rows, the adjacency has {n} nodes"
+        return a.stride(0) if a.shape[0] > 1 else max(a.shape[1], a.stride(0))
+
+    @staticmethod
+    def _softmax_t(t, like):
+        assert t.numel() == 1 and t.dtype == torch.float32 and t.device == like.device, "t: one fp32 on the operand's device"
+        return t.data_ptr()  # read by the kernels when they run: a captured launch follows the parameter
+
+    def softmax_fwd(self, x, t):
+        """(y, lse) = K1s forward: per destination and channel the softmax-weighted mean of the neighbour messages at temperature
+        t (one fp32 on the device), lse = max + log of the weighted sum of exponentials, kept for the backward."""
+        self._need_softmax("softmax_fwd")
+        op = self.fwd
+        ldx = self._softmax_operand(x, op.n_cols, "X")
+        H = x.shape[1]
+        lib = _lib.load()
+        y = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
+        lse = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
+        ws = self._softmax_workspace("fwd", H, lib.glass_spmm_softmax_ws_bytes(op.header.ctypes.data, H))
+        rc = lib.glass_spmm_softmax_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
+                                            self._softmax_t(t, x), y.data_ptr(), H, lse.data_ptr(), H, op.n_rows, H,
+                                            op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
+                                            torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_softmax_csr_f32")
+        return y, lse
+
+    def softmax_bwd(self, dy, x, y, lse, t):
+        """dx of K1s, from the forward's operand x and its results (y, lse)."""
+        self._need_softmax("softmax_bwd")
+        op = self.bwd
+        ldx = self._softmax_operand(x, op.n_rows, "X")
+        lddy, ldy, ldl = (self._softmax_operand(a, op.n_cols, n) for a, n in ((dy, "dY"), (y, "Y"), (lse, "L")))
+        assert dy.shape == x.shape == y.shape == lse.shape
+        H = x.shape[1]
+        lib = _lib.load()
+        dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
+        ws = self._softmax_workspace("bwd", H, lib.glass_spmm_softmax_bwd_ws_bytes(op.header.ctypes.data, H))
+        rc = lib.glass_spmm_softmax_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
+                                            self._softmax_t(t, x), dy.data_ptr(), lddy, y.data_ptr(), ldy, lse.data_ptr(), ldl,
+                                            dx.data_ptr(), H, op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
+                                            ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_softmax_bwd_f32")
+        return dx
+
+    def softmax_dt(self, dy, x, y, lse, t):
+        """The temperature's gradient (shape [1]): a further pass over the forward CSR, run only when t is trained."""
+        self._need_softmax("softmax_dt")
+        op = self.fwd
+        ldx = self._softmax_operand(x, op.n_cols, "X")
+        lddy, ldy, ldl = (self._softmax_operand(a, op.n_rows, n) for a, n in ((dy, "dY"), (y, "Y"), (lse, "L")))
+        assert dy.shape == x.shape == y.shape == lse.shape
+        H = x.shape[1]
+        lib = _lib.load()
+        dt = torch.zeros(1, dtype=torch.float32, device=x.device)
+        ws = self._softmax_workspace("dt", H, lib.glass_spmm_softmax_dt_ws_bytes(op.header.ctypes.data, H))
+        rc = lib.glass_spmm_softmax_dt_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
+                                           self._softmax_t(t, x), dy.data_ptr(), lddy, y.data_ptr(), ldy, lse.data_ptr(), ldl,
+                                           dt.data_ptr(), op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
+                                           ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_softmax_dt_f32")
+        return dt
 
     def to_dense(self):
         """Dense [N,N] (tests on tiny graphs only)."""

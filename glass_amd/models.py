@@ -7,7 +7,8 @@ torch; there is no CPU path.
 Reference map (file:line under /root/reference):
   Seq 10-24 · MLP 27-80 · buildAdj 83-111 · GLASSConv 114-174 · EmbZGConv 177-272 ·
   PoolModule/AddPool/MaxPool/MeanPool/SizePool 275-319 · GLASS 322-355   (impl/models.py)
-Not in the reference: AttnPool (attention readout, pool "attn"); aggr "max" (max neighbour aggregation, buildAdj).
+Not in the reference: AttnPool (attention readout, pool "attn"); aggr "max" (max neighbour aggregation, buildAdj); aggr
+"softmax" (softmax neighbour aggregation with a learned temperature: the conv layers' parameter `t`).
 """
 import torch
 import torch.nn as nn
@@ -143,8 +144,9 @@ def buildAdj(edge_index, edge_weight, n_node: int, aggr: str):
     """Normalised adjacency for aggr in {mean,sum,gcn} as a device CSR (graph.CSRAdj) instead of the
     reference's COO.  One instance is shared by every layer asking for the same (graph, aggr) —
     the reference builds an identical copy per layer (models.py:154-156).  aggr "max" (an extension): the raw weights,
-    aggregated by ops.spmm with a max instead of a sum."""
-    if aggr not in ("mean", "sum", "gcn", "max"):
+    aggregated by ops.spmm with a max instead of a sum.  aggr "softmax" (an extension): the raw weights, strictly positive
+    (ValueError otherwise), aggregated by ops.spmm_softmax with the layer's temperature."""
+    if aggr not in ("mean", "sum", "gcn", "max", "softmax"):
         raise NotImplementedError
     for ei, ew, n, a, adj in _adj_cache:
         if ei is edge_index and ew is edge_weight and n == int(n_node) and a == aggr:
@@ -155,11 +157,18 @@ def buildAdj(edge_index, edge_weight, n_node: int, aggr: str):
     return adj
 
 
+def _reset_softmax_t(conv):
+    """The temperature of a conv layer with aggr "softmax" back to its constructor value (in place: it may live in an arena)."""
+    if conv.aggr == "softmax":
+        with torch.no_grad():
+            conv.t.fill_(conv.softmax_t)
+
+
 class GLASSConv(nn.Module):
     """Labeled message-passing layer: two weight sets (index 1 = labeled, 0 = unlabeled) mixed by
     z_ratio before and after the neighbour aggregation."""
     def __init__(self, in_channels: int, out_channels: int, activation=nn.ReLU(inplace=True), aggr="mean",
-                 z_ratio=0.8, dropout=0.2):
+                 z_ratio=0.8, dropout=0.2, softmax_t=1.0):
         super().__init__()
         self.trans_fns = nn.ModuleList([nn.Linear(in_channels, out_channels), nn.Linear(in_channels, out_channels)])
         self.comb_fns = nn.ModuleList([nn.Linear(in_channels + out_channels, out_channels),
@@ -171,11 +180,15 @@ class GLASSConv(nn.Module):
         self.z_ratio = z_ratio
         self.dropout = dropout
         self.call_base = 0  # set by EmbZGConv: distinguishes dropout streams of different layers
+        self.softmax_t = float(softmax_t)
+        if aggr == "softmax":  # (no other configuration owns the key: their state_dict is unchanged)
+            self.t = nn.Parameter(torch.full((1, ), self.softmax_t))
 
     def reset_parameters(self):
         for lin in list(self.trans_fns) + list(self.comb_fns):
             lin.reset_parameters()
         self.gn.reset_parameters()
+        _reset_softmax_t(self)
 
     def forward(self, x_, edge_index, edge_weight, mask, out=None, batch=None):
         """`out` (optional, fused path only): a preallocated [N,H] view (a slice of the JK buffer) to write into.
@@ -186,7 +199,12 @@ class GLASSConv(nn.Module):
             self.adj = buildAdj(edge_index, edge_weight, x_.shape[0] if batch is None else batch.N, self.aggr)
         if batch is not None and x_.shape[0] != batch.R * batch.N:
             raise ValueError(f"GLASSConv: {x_.shape[0]} rows for {batch!r}")
-        agg = (lambda m: ops.spmm(self.adj, m)) if batch is None else (lambda m: ops.spmm_rep(self.adj, m, batch.R))
+        if batch is not None:
+            agg = lambda m: ops.spmm_rep(self.adj, m, batch.R)
+        elif self.aggr == "softmax":
+            agg = lambda m: ops.spmm_softmax(self.adj, m, self.t)
+        else:
+            agg = lambda m: ops.spmm(self.adj, m)
         rep = {} if batch is None else {"rep": batch}  # (a training pass collects the weight gradients replica by replica)
         if mask.dtype != torch.uint8:
             mask = mask.reshape(-1).to(torch.uint8)
@@ -543,7 +561,7 @@ def _head(pred, emb):
 # ---------------------------------------------------------------------------------------------
 class MyGCNConv(nn.Module):
     """Unlabeled message-passing layer: comb_fn([GraphNorm(adj @ act(trans_fn(x_))) || x_])."""
-    def __init__(self, in_channels: int, out_channels: int, activation=nn.ReLU(inplace=True), aggr="mean"):
+    def __init__(self, in_channels: int, out_channels: int, activation=nn.ReLU(inplace=True), aggr="mean", softmax_t=1.0):
         super().__init__()
         self.trans_fn = Linear(in_channels, out_channels)
         self.comb_fn = Linear(in_channels + out_channels, out_channels)
@@ -551,17 +569,21 @@ class MyGCNConv(nn.Module):
         self.activation = activation
         self.aggr = aggr
         self.gn = GraphNorm(out_channels)
+        self.softmax_t = float(softmax_t)
+        if aggr == "softmax":
+            self.t = nn.Parameter(torch.full((1, ), self.softmax_t))
 
     def reset_parameters(self):
         self.trans_fn.reset_parameters()
         self.comb_fn.reset_parameters()
         self.gn.reset_parameters()
+        _reset_softmax_t(self)
 
     def forward(self, x_, edge_index, edge_weight):
         if self.adj is None:
             self.adj = buildAdj(edge_index, edge_weight, x_.shape[0], self.aggr)
         x = self.activation(self.trans_fn(x_))
-        x = self.gn(ops.spmm(self.adj, x))
+        x = self.gn(ops.spmm_softmax(self.adj, x, self.t) if self.aggr == "softmax" else ops.spmm(self.adj, x))
         return self.comb_fn(torch.cat((x, x_), dim=-1))
 
 

@@ -183,9 +183,41 @@ class SpMMMaxFn(torch.autograd.Function):
         return None, ctx.adj.max_bwd(dy, arg)
 
 
+class SpMMSoftmaxFn(torch.autograd.Function):
+    """y[i] = softmax-weighted mean of the messages val, x[col] over the entries of row i of A at temperature t (aggr "softmax",
+    K1s: csrc/spmm_softmax.hip).  The node keeps x, y and the log-sum-exp; the backward launches the dX pass and the dt pass
+    only for the input that needs a gradient (A carries none)."""
+    @staticmethod
+    def forward(ctx, adj, x, t):
+        _need_gpu(x)
+        x, _ = _rows(x)
+        y, lse = adj.softmax_fwd(x, t)
+        ctx.adj = adj
+        ctx.save_for_backward(x, y, lse, t)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy, _ = _rows(dy)
+        x, y, lse, t = ctx.saved_tensors
+        dx = ctx.adj.softmax_bwd(dy, x, y, lse, t) if ctx.needs_input_grad[1] else None
+        dt = ctx.adj.softmax_dt(dy, x, y, lse, t).view_as(t) if ctx.needs_input_grad[2] else None
+        return None, dx, dt
+
+
+def spmm_softmax(adj, x, t):
+    """Softmax neighbour aggregation: `adj` a graph.CSRAdj built for aggr "softmax", t one fp32 on the device (a parameter, or
+    any tensor of one element)."""
+    if getattr(adj, "aggr", None) != "softmax":
+        raise GlassHipError(f"spmm_softmax: the adjacency was built for aggr {getattr(adj, 'aggr', None)!r}, not 'softmax'")
+    return SpMMSoftmaxFn.apply(adj, x, t)
+
+
 def spmm(adj, x):
     if getattr(adj, "aggr", None) == "max":
         return SpMMMaxFn.apply(adj, x)
+    if getattr(adj, "aggr", None) == "softmax":
+        raise GlassHipError("spmm: a softmax adjacency has no temperature of its own; call ops.spmm_softmax(adj, x, t)")
     return SpMMFn.apply(adj, x)
 
 
@@ -999,6 +1031,9 @@ class SpMMRepFn(torch.autograd.Function):
 def spmm_rep(adj, x, R):
     if getattr(adj, "aggr", None) == "max":
         raise GlassHipError("replicated max aggregation is not built: aggr 'max' runs one graph at a time (no exact "
+                            "zero-one labels / --use_zeroone with it)")
+    if getattr(adj, "aggr", None) == "softmax":
+        raise GlassHipError("replicated softmax aggregation is not built: aggr 'softmax' runs one graph at a time (no exact "
                             "zero-one labels / --use_zeroone with it)")
     return SpMMRepFn.apply(adj, x, int(R))
 

@@ -583,8 +583,10 @@ class StackProgram:
     @staticmethod
     def supported(emb):
         from .models import GLASSConv, EmbGConv, _act_code
-        if any(getattr(c, "aggr", None) == "max" for c in emb.convs):
-            return False  # max aggregation is not a product: no fused form, the per-op path (ops.spmm -> K1m) serves it
+        if any(getattr(c, "aggr", None) in ("max", "softmax") for c in emb.convs):
+            # max and softmax aggregation are no products: no fused form, the per-op path (ops.spmm -> K1m,
+            # ops.spmm_softmax -> K1s) serves them
+            return False
         if isinstance(emb, EmbGConv):
             return StackProgram.supported_unlabeled(emb)
         if not ops.USE_FUSED_DENSE or getattr(emb, "_glass_arena", None) is None or emb.gns is None:

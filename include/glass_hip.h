@@ -131,6 +131,57 @@ int glass_spmm_max_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const 
                            int64_t n_rows, int64_t H,
                            const int32_t* plan_t_header_host, const int32_t* plan_t_dev, void* ws, void* stream);
 
+/* K1s softmax neighbour aggregation with a temperature (aggr "softmax": an extension, the reference has none; DeeperGCN,
+ *     PyG's SoftmaxAggregation) at the call site K1 serves, on K1's CSR and plans.  Forward CSR as for K1m: entries sorted by
+ *     (row, col), stable, duplicates kept, row = destination; val = the raw edge weights, which act as multiplicities and must
+ *     be > 0 (the caller's check: the kernels do not test it).  t_dev points to ONE fp32 in device memory, read by the kernels
+ *     when they run — a captured launch sees the value of the moment of its replay.
+ *
+ *   glass_spmm_softmax_csr_f32: with s_e = t * X[col[e],c] (one rounded fp32 multiply), M = max_e s_e,
+ *     Z = sum_e val[e] exp(s_e - M):   Y[i,c] = (sum_e val[e] exp(s_e - M) X[col[e],c]) / Z,   L[i,c] = M + log Z.
+ *     A row without entries: Y = 0, L = 0.  t = 0 is the weighted mean; t -> inf tends to the max.  The max is always
+ *     subtracted: nothing overflows while t * X is finite (the precondition).  Lane groups, the four waves of a long-row
+ *     item and the chunks of a cut row merge their (M, Z, S) triples in a fixed order: bitwise repeatable for a given plan
+ *     (not identical across plans: it is a sum).  ws: glass_spmm_softmax_ws_bytes(hdr, H) = the plan's partial slots times H
+ *     triples; cut rows are merged by a second launch in slot order.
+ *   glass_spmm_softmax_bwd_f32: on the TRANSPOSED CSR (row j = source, col_t = destinations i, val_t, its own plan), with
+ *     p = val_t * exp(t * X[j,c] - L[i,c])  (0 < p <= 1; one exponential of the difference):
+ *     dX[j,c] = sum over the entries of row j of p * dY[i,c] * (1 + t * (X[j,c] - Y[i,c])), in a fixed order (no float
+ *     atomics, bitwise repeatable).  Row j's own X row is read once; per entry three [H] rows of the destination (dY, Y, L).
+ *     ws: glass_spmm_softmax_bwd_ws_bytes(hdr_t, H).
+ *   glass_spmm_softmax_dt_f32: the temperature's gradient, on the FORWARD CSR:
+ *     dt[0] = sum over i, c, e of dY[i,c] * p_e * x_e * (x_e - Y[i,c]),  x_e = X[col[e],c],  p_e = val[e] exp(t x_e - L[i,c]).
+ *     One fp64 partial per plan item and column tile, summed in fp64 in a fixed order by a one-workgroup launch, written as
+ *     one fp32.  ws (8-byte aligned): glass_spmm_softmax_dt_ws_bytes(hdr, H).  n_rows == 0 leaves dt untouched.
+ *   All three: every H and leading dimension K1m takes (16-byte vector form when H, the ld* and the pointers allow it, scalar
+ *     form otherwise).  Refused on the host before any launch: null or misaligned pointers, H <= 0, ld* < H, partial slots
+ *     (dt: plan items) without ws -> GLASS_E_ARG; a header that is no plan for n_rows -> GLASS_E_PLAN; H beyond 65535 * 64
+ *     columns -> GLASS_E_UNSUPPORTED.  n_rows == 0 returns 0 without a launch.  The *_ws_bytes queries: GLASS_E_PLAN for a
+ *     header that is no plan, GLASS_E_ARG for H <= 0. */
+int64_t glass_spmm_softmax_ws_bytes(const int32_t* plan_header_host, int64_t H);
+int glass_spmm_softmax_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val, /* CSR of A, device */
+                               const float* X, int64_t ldx,                                 /* [n_cols, H] */
+                               const float* t_dev,                                          /* one fp32, device */
+                               float* Y, int64_t ldy, float* L, int64_t ldl,                /* [n_rows, H] each */
+                               int64_t n_rows, int64_t H,
+                               const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_spmm_softmax_bwd_ws_bytes(const int32_t* plan_t_header_host, int64_t H);
+int glass_spmm_softmax_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* val_t,   /* CSR of A^T */
+                               const float* X, int64_t ldx,                                         /* [n_rows, H] */
+                               const float* t_dev,
+                               const float* dY, int64_t lddy, const float* Y, int64_t ldy,          /* [n_cols of A^T, H] each */
+                               const float* L, int64_t ldl,
+                               float* dX, int64_t lddx,                                             /* [n_rows, H] */
+                               int64_t n_rows, int64_t H,
+                               const int32_t* plan_t_header_host, const int32_t* plan_t_dev, void* ws, void* stream);
+int64_t glass_spmm_softmax_dt_ws_bytes(const int32_t* plan_header_host, int64_t H);
+int glass_spmm_softmax_dt_f32(const int32_t* rowptr, const int32_t* col, const float* val,          /* CSR of A */
+                              const float* X, int64_t ldx, const float* t_dev,
+                              const float* dY, int64_t lddy, const float* Y, int64_t ldy, const float* L, int64_t ldl,
+                              float* dt,                                                            /* one fp32, device */
+                              int64_t n_rows, int64_t H,
+                              const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+
 /* K2  normalised edge values of buildAdj (impl/models.py:83-111) on an (row,col)-sorted COO:
  *     deg = segment-sum of w per row, deg<0.5 -> +1; aggr 0=mean w/deg[row], 1=sum w,
  *     2=gcn deg[row]^-1/2 * w * deg[col]^-1/2.  Duplicate (row,col) entries stay separate CSR
