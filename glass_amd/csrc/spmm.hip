@@ -296,25 +296,6 @@ extern "C" int glass_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, con
                      (hdr[H_NSLOTS] == 0 || aligned16(ws));
 #define GLASS_SPMM_CASE(VW, LPR) \
     return launch_spmm<VW, LPR>(rowptr, col, val, X, ldx, Y, ldy, H, hdr, plan_dev, wsf, st)
-    if (vec) {
-        switch (pow2_ceil_cap(H / 4, 64)) {
-            case 1: GLASS_SPMM_CASE(4, 1);
-            case 2: GLASS_SPMM_CASE(4, 2);
-            case 4: GLASS_SPMM_CASE(4, 4);
-            case 8: GLASS_SPMM_CASE(4, 8);
-            case 16: GLASS_SPMM_CASE(4, 16);
-            case 32: GLASS_SPMM_CASE(4, 32);
-            default: GLASS_SPMM_CASE(4, 64);
-        }
-    }
-    switch (pow2_ceil_cap(H, 64)) {
-        case 1: GLASS_SPMM_CASE(1, 1);
-        case 2: GLASS_SPMM_CASE(1, 2);
-        case 4: GLASS_SPMM_CASE(1, 4);
-        case 8: GLASS_SPMM_CASE(1, 8);
-        case 16: GLASS_SPMM_CASE(1, 16);
-        case 32: GLASS_SPMM_CASE(1, 32);
-        default: GLASS_SPMM_CASE(1, 64);
-    }
+    GLASS_K1_WIDTH_DISPATCH(vec, H, GLASS_SPMM_CASE);
 #undef GLASS_SPMM_CASE
 }

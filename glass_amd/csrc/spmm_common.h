@@ -23,6 +23,34 @@ typedef float k1_f32x4 __attribute__((ext_vector_type(4)));
 enum { H_MAGIC, H_VER, H_NROWS, H_NNZ, H_NSWEEP, H_NLONG, H_NREDUCE, H_NSLOTS, H_LONG_THR, H_LONG_CHUNK,
        H_OFF_SWEEP, H_OFF_LONG, H_OFF_REDUCE, H_RP_FACTOR, H_MIN_ITEM_DEG, H_FLAT_SHARE };
 
+// ---- width dispatch (host) ---------------------------------------------------------------------
+// A feature row of H floats is LPR lanes x VW floats: VW = 4 where the caller found 16-byte accesses possible (`vec`), else 1;
+// LPR the power of two that covers the row, at most one wave (wider rows go in column tiles).  CASE(VW, LPR) is the caller's
+// statement for one of the fourteen builds and must return.
+#define GLASS_K1_WIDTH_DISPATCH(vec, H, CASE)      \
+    do {                                           \
+        if (vec) {                                 \
+            switch (pow2_ceil_cap((H) / 4, 64)) {  \
+                case 1: CASE(4, 1);                \
+                case 2: CASE(4, 2);                \
+                case 4: CASE(4, 4);                \
+                case 8: CASE(4, 8);                \
+                case 16: CASE(4, 16);              \
+                case 32: CASE(4, 32);              \
+                default: CASE(4, 64);              \
+            }                                      \
+        }                                          \
+        switch (pow2_ceil_cap((H), 64)) {          \
+            case 1: CASE(1, 1);                    \
+            case 2: CASE(1, 2);                    \
+            case 4: CASE(1, 4);                    \
+            case 8: CASE(1, 8);                    \
+            case 16: CASE(1, 16);                  \
+            case 32: CASE(1, 32);                  \
+            default: CASE(1, 64);                  \
+        }                                          \
+    } while (0)
+
 // ---- vector helpers --------------------------------------------------------------------------
 template <int VW> struct Vec;
 template <> struct Vec<4> {

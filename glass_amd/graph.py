@@ -170,26 +170,25 @@ class CSRAdj:
         self.bwd = CSROperand(rowptr_t, col_t, val_t, n, n)
         if aggr == "max":
             self.eid_t = perm_t.to(torch.int32).contiguous()  # transposed entry t is forward entry eid_t[t]
-            self._max_ws = {}
-            self._retired_ws = []
-        if aggr == "softmax":
-            self._softmax_ws = {}
+        if aggr in ("max", "softmax"):
+            self._aggr_ws = {}
             self._retired_ws = []
 
     @property
     def nnz(self):
         return self.fwd.nnz
 
-    def _max_workspace(self, kind, H, nbytes):
-        """Partial rows of K1m's cut rows: one buffer per direction, feature width and branch (set_workspace_branch)."""
+    def _aggr_workspace(self, entry, H, nbytes):
+        """Workspaces of K1m and K1s (partial pairs / triples / rows of cut rows, the fp64 partials of "softmax_dt"): one
+        8-byte aligned buffer per entry, feature width and branch (set_workspace_branch)."""
         if nbytes < 0:
             raise _lib.GlassHipError("bad plan header")
-        key = (kind, H, _ws_branch)
-        ws = self._max_ws.get(key)
-        if ws is None or ws.numel() * 4 < nbytes:
+        key = (entry, H, _ws_branch)
+        ws = self._aggr_ws.get(key)
+        if ws is None or ws.numel() * 8 < nbytes:
             if ws is not None:
                 self._retired_ws.append(ws)  # (a captured graph may still launch with this pointer: never handed back)
-            ws = self._max_ws[key] = torch.empty(max(nbytes // 4, 4), dtype=torch.int32, device=self.fwd.rowptr.device)
+            ws = self._aggr_ws[key] = torch.empty(max((nbytes + 7) // 8, 2), dtype=torch.float64, device=self.fwd.rowptr.device)
         return ws
 
     def _need_max(self, what):
@@ -207,7 +206,7 @@ class CSRAdj:
         lib = _lib.load()
         y = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
         arg = torch.empty((op.n_rows, H), dtype=torch.int32, device=x.device)
-        ws = self._max_workspace("fwd", H, lib.glass_spmm_max_ws_bytes(op.header.ctypes.data, H))
+        ws = self._aggr_workspace("max_fwd", H, lib.glass_spmm_max_ws_bytes(op.header.ctypes.data, H))
         ldx = x.stride(0) if x.shape[0] > 1 else max(H, x.stride(0))
         rc = lib.glass_spmm_max_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
                                         y.data_ptr(), H, arg.data_ptr(), H, op.n_rows, H, op.header.ctypes.data,
@@ -224,7 +223,7 @@ class CSRAdj:
         H = dy.shape[1]
         lib = _lib.load()
         dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=dy.device)
-        ws = self._max_workspace("bwd", H, lib.glass_spmm_max_bwd_ws_bytes(op.header.ctypes.data, H))
+        ws = self._aggr_workspace("max_bwd", H, lib.glass_spmm_max_bwd_ws_bytes(op.header.ctypes.data, H))
         ldy = dy.stride(0) if dy.shape[0] > 1 else max(H, dy.stride(0))
         lda = arg.stride(0) if arg.shape[0] > 1 else max(H, arg.stride(0))
         rc = lib.glass_spmm_max_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
@@ -233,19 +232,6 @@ class CSRAdj:
                                         torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "glass_spmm_max_bwd_f32")
         return dx
-
-    def _softmax_workspace(self, kind, H, nbytes):
-        """Workspaces of K1s: one buffer per entry ("fwd": partial triples, "bwd": partial rows, "dt": fp64 partials), feature
-        width and branch (set_workspace_branch)."""
-        if nbytes < 0:
-            raise _lib.GlassHipError("bad plan header")
-        key = (kind, H, _ws_branch)
-        ws = self._softmax_ws.get(key)
-        if ws is None or ws.numel() * 8 < nbytes:
-            if ws is not None:
-                self._retired_ws.append(ws)  # (a captured graph may still launch with this pointer: never handed back)
-            ws = self._softmax_ws[key] = torch.empty(max((nbytes + 7) // 8, 2), dtype=torch.float64, device=self.fwd.rowptr.device)
-        return ws
 
     def _need_softmax(self, what):
         if self.aggr != "softmax":
@@ -272,7 +258,7 @@ class CSRAdj:
         lib = _lib.load()
         y = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
         lse = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
-        ws = self._softmax_workspace("fwd", H, lib.glass_spmm_softmax_ws_bytes(op.header.ctypes.data, H))
+        ws = self._aggr_workspace("softmax_fwd", H, lib.glass_spmm_softmax_ws_bytes(op.header.ctypes.data, H))
         rc = lib.glass_spmm_softmax_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
                                             self._softmax_t(t, x), y.data_ptr(), H, lse.data_ptr(), H, op.n_rows, H,
                                             op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
@@ -290,7 +276,7 @@ class CSRAdj:
         H = x.shape[1]
         lib = _lib.load()
         dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
-        ws = self._softmax_workspace("bwd", H, lib.glass_spmm_softmax_bwd_ws_bytes(op.header.ctypes.data, H))
+        ws = self._aggr_workspace("softmax_bwd", H, lib.glass_spmm_softmax_bwd_ws_bytes(op.header.ctypes.data, H))
         rc = lib.glass_spmm_softmax_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
                                             self._softmax_t(t, x), dy.data_ptr(), lddy, y.data_ptr(), ldy, lse.data_ptr(), ldl,
                                             dx.data_ptr(), H, op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
@@ -308,7 +294,7 @@ class CSRAdj:
         H = x.shape[1]
         lib = _lib.load()
         dt = torch.zeros(1, dtype=torch.float32, device=x.device)
-        ws = self._softmax_workspace("dt", H, lib.glass_spmm_softmax_dt_ws_bytes(op.header.ctypes.data, H))
+        ws = self._aggr_workspace("softmax_dt", H, lib.glass_spmm_softmax_dt_ws_bytes(op.header.ctypes.data, H))
         rc = lib.glass_spmm_softmax_dt_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
                                            self._softmax_t(t, x), dy.data_ptr(), lddy, y.data_ptr(), ldy, lse.data_ptr(), ldl,
                                            dt.data_ptr(), op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
