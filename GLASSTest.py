@@ -52,16 +52,21 @@ def parse_args(argv=None):
                         "split's label counts, applied inside the fused loss (default: none)")
     p.add_argument("--pool", type=str, default=None, choices=tuple(POOLS),
                    help="(extension) readout instead of the config file's `pool` (default: the config's value)")
-    p.add_argument("--aggr", type=str, default=None, choices=("mean", "sum", "gcn", "max", "softmax"),
+    p.add_argument("--aggr", type=str, default=None, choices=("mean", "sum", "gcn", "max", "softmax", "gat"),
                    help="(extension) neighbour aggregation instead of the config file's `aggr` (default: the config's value); "
                         "max: the largest weighted neighbour message per channel; softmax: the softmax-weighted mean of the "
-                        "messages with a learned temperature per layer (positive edge weights); neither is available with "
-                        "--use_zeroone")
+                        "messages with a learned temperature per layer (positive edge weights); gat: single-head attention, "
+                        "the weights from two learned vectors per layer (positive edge weights); none of the three is available "
+                        "with --use_zeroone")
+    p.add_argument("--gat_slope", type=float, default=0.2,
+                   help="(extension) LeakyReLU's negative slope in the attention scores of --aggr gat (default: 0.2)")
     args = p.parse_args(argv)
     if args.use_zeroone and args.use_maxzeroone:
         p.error("--use_zeroone and --use_maxzeroone are mutually exclusive")
     if args.clip is not None and not args.clip > 0:
         p.error("--clip must be positive")
+    if args.gat_slope != args.gat_slope:
+        p.error("--gat_slope must be a number")
     return args
 
 
@@ -139,7 +144,8 @@ class Run:
         def build(h):
             conv = models.EmbZGConv(h, h, conv_layer, max_deg=self.max_deg,
                                     activation=nn.ELU(inplace=True), jk=jk, dropout=dropout,
-                                    conv=functools.partial(models.GLASSConv, aggr=aggr, z_ratio=z_ratio, dropout=dropout),
+                                    conv=functools.partial(models.GLASSConv, aggr=aggr, z_ratio=z_ratio, dropout=dropout,
+                                                           gat_slope=getattr(a, "gat_slope", 0.2)),
                                     gn=True)
             if a.use_nodeid:
                 print("load ", f"./Emb/{a.dataset}_{hidden_dim}.pt")

@@ -82,6 +82,18 @@ SIGNATURES = {
     "glass_spmm_softmax_bwd_f32": (c_int, [_P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
     "glass_spmm_softmax_dt_ws_bytes": (c_int64, [_P, _I]),
     "glass_spmm_softmax_dt_f32": (c_int, [_P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "glass_gat_scores_f32": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _P]),
+    "glass_spmm_gat_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_gat_csr_f32": (c_int, [_P, _P, _P, _P, _I, _P, _P, c_float, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "glass_spmm_gat_edge_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_gat_edge_f32": (c_int, [_P, _P, _P, _P, _I, _P, _P, c_float, _P, _I, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "glass_spmm_gat_bwd_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_gat_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P,
+                                       _P]),
+    "glass_spmm_gat_da_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_gat_da_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, c_int, _P, _P, _P, _P]),
+    "glass_gat_datt_ws_bytes": (c_int64, [_I, _I]),
+    "glass_gat_datt_f32": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
     "glass_adj_values_f32": (c_int, [_P, _P, _P, _I, c_int, _P, _P, _P]),
     "glass_maxzoz_i64": (c_int, [_P, _I, _P, _I, _P]),
     "glass_embed_label_f32": (c_int, [_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _P]),

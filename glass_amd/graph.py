@@ -9,8 +9,8 @@ HBM layout (all on the device the graph lives on):
   rowptr int32[N+1], col int32[nnz], val fp32[nnz]            CSR of A   (row = destination)
   rowptr_t, col_t, val_t                                      CSR of A^T (for the backward)
   plan / plan_t int32[...]                                    opaque K1 schedules
-  eid_t int32[nnz]                                            aggr "max" only: forward index of each entry of A^T
-aggr "max" and "softmax" keep the raw edge weights in val (the values of "sum"); "softmax" requires them > 0.
+  eid_t int32[nnz]                                            aggr "max" and "gat": forward index of each entry of A^T
+aggr "max", "softmax" and "gat" keep the raw edge weights in val (the values of "sum"); "softmax" and "gat" require them > 0.
 Duplicate (row,col) entries are kept as separate entries: they add up in the product exactly as in
 the reference's uncoalesced COO matmul.
 """
@@ -133,9 +133,10 @@ class CSRAdj:
     """Normalised adjacency A (forward) and A^T (backward) for one aggregation scheme.  aggr "max" (an extension): the raw
     edge weights (the values of "sum"), aggregated by K1m (max_fwd / max_bwd) instead of K1's product.  aggr "softmax" (an
     extension): the raw weights too, strictly positive (checked here, once), aggregated by K1s (softmax_fwd / softmax_bwd /
-    softmax_dt) with a temperature the caller owns."""
+    softmax_dt) with a temperature the caller owns.  aggr "gat" (an extension): built like "softmax", aggregated by K1a
+    (gat_scores / gat_fwd / gat_edge / gat_bwd / gat_datt) with two attention vectors the caller owns."""
     def __init__(self, edge_index, edge_weight, n_node, aggr):
-        if aggr not in _lib.AGGR_MODES and aggr not in ("max", "softmax"):
+        if aggr not in _lib.AGGR_MODES and aggr not in ("max", "softmax", "gat"):
             raise NotImplementedError  # same error type as the reference (models.py:110-111)
         if not edge_index.is_cuda:
             raise _lib.GlassHipError("glass_amd runs on the GPU only (edge_index is on %s); the CPU path lives in "
@@ -149,14 +150,14 @@ class CSRAdj:
         perm = torch.argsort(row * n + col, stable=True)
         row, col = row[perm], col[perm]
         w = edge_weight.to(torch.float32)[perm].contiguous()
-        if aggr == "softmax" and not bool((w > 0).all()):  # one device read; the kernels do not test it
-            raise ValueError("aggr 'softmax': edge weights are multiplicities and must be strictly positive")
+        if aggr in ("softmax", "gat") and not bool((w > 0).all()):  # one device read; the kernels do not test it
+            raise ValueError(f"aggr {aggr!r}: edge weights are multiplicities and must be strictly positive")
         rowptr = _csr_from_sorted(row, n)
         col32 = col.to(torch.int32).contiguous()
         self.deg = torch.empty(n, dtype=torch.float32, device=dev)
         val = torch.empty(nnz, dtype=torch.float32, device=dev)
         rc = _lib.load().glass_adj_values_f32(rowptr.data_ptr(), col32.data_ptr(), w.data_ptr(), n,
-                                              _lib.AGGR_MODES["sum" if aggr in ("max", "softmax") else aggr], self.deg.data_ptr(),
+                                              _lib.AGGR_MODES["sum" if aggr in ("max", "softmax", "gat") else aggr], self.deg.data_ptr(),
                                               val.data_ptr(),
                                               torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "glass_adj_values_f32")
@@ -168,9 +169,9 @@ class CSRAdj:
         self.n_node, self.aggr = n, aggr
         self.fwd = CSROperand(rowptr, col32, val, n, n)
         self.bwd = CSROperand(rowptr_t, col_t, val_t, n, n)
-        if aggr == "max":
+        if aggr in ("max", "gat"):
             self.eid_t = perm_t.to(torch.int32).contiguous()  # transposed entry t is forward entry eid_t[t]
-        if aggr in ("max", "softmax"):
+        if aggr in ("max", "softmax", "gat"):
             self._aggr_ws = {}
             self._retired_ws = []
 
@@ -179,7 +180,7 @@ class CSRAdj:
         return self.fwd.nnz
 
     def _aggr_workspace(self, entry, H, nbytes):
-        """Workspaces of K1m and K1s (partial pairs / triples / rows of cut rows, the fp64 partials of "softmax_dt"): one
+        """Workspaces of K1m, K1s and K1a (partial pairs / triples / rows of cut rows, the fp64 partials of "softmax_dt" and "gat_datt"): one
         8-byte aligned buffer per entry, feature width and branch (set_workspace_branch)."""
         if nbytes < 0:
             raise _lib.GlassHipError("bad plan header")
@@ -301,6 +302,123 @@ class CSRAdj:
                                            ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "glass_spmm_softmax_dt_f32")
         return dt
+
+    def _need_gat(self, what):
+        if self.aggr != "gat":
+            raise _lib.GlassHipError(f"CSRAdj.{what}: this adjacency was built for aggr {self.aggr!r}, not 'gat'")
+
+    def _gat_vec(self, v, n, name):
+        assert v.dim() == 1 and v.shape[0] == n and v.stride(0) == 1 and v.dtype == torch.float32 and v.is_cuda, \
+            f"{name}: {n} contiguous fp32 on the device"
+        return v.data_ptr()  # read by the kernels when they run: a captured launch follows the parameter
+
+    def gat_scores(self, x, att_src, att_dst):
+        """(a, b) = K1a node scores: a = x @ att_src, b = x @ att_dst, [N] each (fp64 sums, rounded once)."""
+        self._need_gat("gat_scores")
+        ldx = self._softmax_operand(x, self.n_node, "X")
+        H = x.shape[1]
+        a = torch.empty(self.n_node, dtype=torch.float32, device=x.device)
+        b = torch.empty(self.n_node, dtype=torch.float32, device=x.device)
+        rc = _lib.load().glass_gat_scores_f32(x.data_ptr(), ldx, self._gat_vec(att_src, H, "att_src"),
+                                              self._gat_vec(att_dst, H, "att_dst"), a.data_ptr(), b.data_ptr(), self.n_node, H,
+                                              torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_gat_scores_f32")
+        return a, b
+
+    def gat_fwd(self, x, a, b, slope):
+        """(y, lse) = K1a forward: per destination the attention-weighted mean of the neighbour messages, the weights a softmax
+        over the row's entries of LeakyReLU(a[source] + b[destination]); lse [N] = max + log of the weighted sum of
+        exponentials, kept for the backward."""
+        self._need_gat("gat_fwd")
+        op = self.fwd
+        ldx = self._softmax_operand(x, op.n_cols, "X")
+        H = x.shape[1]
+        lib = _lib.load()
+        y = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
+        lse = torch.empty(op.n_rows, dtype=torch.float32, device=x.device)
+        ws = self._aggr_workspace("gat_fwd", H, lib.glass_spmm_gat_ws_bytes(op.header.ctypes.data, H))
+        rc = lib.glass_spmm_gat_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
+                                        self._gat_vec(a, op.n_cols, "a"), self._gat_vec(b, op.n_rows, "b"), float(slope),
+                                        y.data_ptr(), H, lse.data_ptr(), op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
+                                        ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_gat_csr_f32")
+        return y, lse
+
+    def gat_edge(self, dy, x, y, lse, a, b, slope):
+        """(g, db) = K1a edge pass over the forward CSR: g [nnz] the score gradient of every entry, in forward entry order (a
+        sampled dense-dense product: per entry the dot of dy[destination] and x[source]), db [N] its row sums."""
+        self._need_gat("gat_edge")
+        op = self.fwd
+        ldx = self._softmax_operand(x, op.n_cols, "X")
+        lddy, ldy = (self._softmax_operand(t, op.n_rows, n) for t, n in ((dy, "dY"), (y, "Y")))
+        assert dy.shape == x.shape == y.shape
+        H = x.shape[1]
+        lib = _lib.load()
+        g = torch.empty(max(op.nnz, 1), dtype=torch.float32, device=x.device)[:op.nnz]
+        db = torch.empty(op.n_rows, dtype=torch.float32, device=x.device)
+        ws = self._aggr_workspace("gat_edge", H, lib.glass_spmm_gat_edge_ws_bytes(op.header.ctypes.data, H))
+        rc = lib.glass_spmm_gat_edge_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
+                                         self._gat_vec(a, op.n_cols, "a"), self._gat_vec(b, op.n_rows, "b"), float(slope),
+                                         dy.data_ptr(), lddy, y.data_ptr(), ldy, self._gat_vec(lse, op.n_rows, "L"), g.data_ptr(),
+                                         db.data_ptr(), op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
+                                         torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_gat_edge_f32")
+        return g, db
+
+    def gat_bwd(self, dy, lse, a, b, g, db, att_src, att_dst, slope):
+        """(dx, da) = K1a transposed pass: dx[j] = the attention-weighted sum of dy over the entries that read x[j], plus
+        da[j] att_src + db[j] att_dst; da [N] = the sums of g over those entries."""
+        self._need_gat("gat_bwd")
+        op = self.bwd
+        lddy = self._softmax_operand(dy, op.n_cols, "dY")
+        H = dy.shape[1]
+        lib = _lib.load()
+        dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=dy.device)
+        da = torch.empty(op.n_rows, dtype=torch.float32, device=dy.device)
+        assert g.dtype == torch.float32 and g.shape == (op.nnz, ) and g.stride(0) == 1
+        ws = self._aggr_workspace("gat_bwd", H, lib.glass_spmm_gat_bwd_ws_bytes(op.header.ctypes.data, H))
+        rc = lib.glass_spmm_gat_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
+                                        self._gat_vec(a, op.n_rows, "a"), self._gat_vec(b, op.n_cols, "b"), float(slope),
+                                        dy.data_ptr(), lddy, self._gat_vec(lse, op.n_cols, "L"), g.data_ptr(),
+                                        self._gat_vec(db, op.n_rows, "db"), self._gat_vec(att_src, H, "att_src"),
+                                        self._gat_vec(att_dst, H, "att_dst"), dx.data_ptr(), H, da.data_ptr(), op.n_rows, H,
+                                        op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
+                                        torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_gat_bwd_f32")
+        return dx, da
+
+    def gat_da(self, g, dy):
+        """da alone (gat_bwd's second result, the same bits) when no dx is wanted; dy only names the lane layout gat_bwd would
+        take (its width, stride and alignment)."""
+        self._need_gat("gat_da")
+        op = self.bwd
+        lddy = self._softmax_operand(dy, op.n_cols, "dY")
+        H = dy.shape[1]
+        lib = _lib.load()
+        da = torch.empty(op.n_rows, dtype=torch.float32, device=g.device)
+        assert g.dtype == torch.float32 and g.shape == (op.nnz, ) and g.stride(0) == 1
+        ws = self._aggr_workspace("gat_da", H, lib.glass_spmm_gat_da_ws_bytes(op.header.ctypes.data, H))
+        vec = H % 4 == 0 and lddy % 4 == 0 and dy.data_ptr() % 16 == 0  # (gat_bwd's own dx and workspace are 16-byte aligned)
+        rc = lib.glass_spmm_gat_da_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
+                                       g.data_ptr(), da.data_ptr(), op.n_rows, H, int(vec), op.header.ctypes.data,
+                                       op.plan.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_gat_da_f32")
+        return da
+
+    def gat_datt(self, x, da, db):
+        """(datt_src, datt_dst) = x^T da, x^T db: the attention vectors' gradients, run only when they are trained."""
+        self._need_gat("gat_datt")
+        ldx = self._softmax_operand(x, self.n_node, "X")
+        H = x.shape[1]
+        lib = _lib.load()
+        ds = torch.zeros(H, dtype=torch.float32, device=x.device)
+        dd = torch.zeros(H, dtype=torch.float32, device=x.device)
+        ws = self._aggr_workspace("gat_datt", H, lib.glass_gat_datt_ws_bytes(self.n_node, H))
+        rc = lib.glass_gat_datt_f32(x.data_ptr(), ldx, self._gat_vec(da, self.n_node, "da"), self._gat_vec(db, self.n_node, "db"),
+                                    ds.data_ptr(), dd.data_ptr(), self.n_node, H, ws.data_ptr(),
+                                    torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_gat_datt_f32")
+        return ds, dd
 
     def to_dense(self):
         """Dense [N,N] (tests on tiny graphs only)."""

@@ -8,7 +8,8 @@ Reference map (file:line under /root/reference):
   Seq 10-24 · MLP 27-80 · buildAdj 83-111 · GLASSConv 114-174 · EmbZGConv 177-272 ·
   PoolModule/AddPool/MaxPool/MeanPool/SizePool 275-319 · GLASS 322-355   (impl/models.py)
 Not in the reference: AttnPool (attention readout, pool "attn"); aggr "max" (max neighbour aggregation, buildAdj); aggr
-"softmax" (softmax neighbour aggregation with a learned temperature: the conv layers' parameter `t`).
+"softmax" (softmax neighbour aggregation with a learned temperature: the conv layers' parameter `t`); aggr "gat" (single-head
+attention aggregation: GLASSConv's parameters `att_src` and `att_dst`).
 """
 import torch
 import torch.nn as nn
@@ -146,7 +147,7 @@ def buildAdj(edge_index, edge_weight, n_node: int, aggr: str):
     the reference builds an identical copy per layer (models.py:154-156).  aggr "max" (an extension): the raw weights,
     aggregated by ops.spmm with a max instead of a sum.  aggr "softmax" (an extension): the raw weights, strictly positive
     (ValueError otherwise), aggregated by ops.spmm_softmax with the layer's temperature."""
-    if aggr not in ("mean", "sum", "gcn", "max", "softmax"):
+    if aggr not in ("mean", "sum", "gcn", "max", "softmax", "gat"):  # ("gat", an extension: built like "softmax", ops.spmm_gat)
         raise NotImplementedError
     for ei, ew, n, a, adj in _adj_cache:
         if ei is edge_index and ew is edge_weight and n == int(n_node) and a == aggr:
@@ -164,11 +165,21 @@ def _reset_softmax_t(conv):
             conv.t.fill_(conv.softmax_t)
 
 
+def _reset_gat_att(conv):
+    """The attention vectors of a conv layer with aggr "gat": xavier_uniform_ on their [1, H] views (in place)."""
+    if conv.aggr == "gat":
+        with torch.no_grad():
+            nn.init.xavier_uniform_(conv.att_src.view(1, -1))
+            nn.init.xavier_uniform_(conv.att_dst.view(1, -1))
+
+
 class GLASSConv(nn.Module):
     """Labeled message-passing layer: two weight sets (index 1 = labeled, 0 = unlabeled) mixed by
-    z_ratio before and after the neighbour aggregation."""
+    z_ratio before and after the neighbour aggregation.  aggr "gat" (an extension): single-head attention over the mixed
+    messages, the layer owns att_src and att_dst ([out_channels] each) and the constant gat_slope (LeakyReLU's negative
+    slope); multi-head attention (heads > 1) is out of scope."""
     def __init__(self, in_channels: int, out_channels: int, activation=nn.ReLU(inplace=True), aggr="mean",
-                 z_ratio=0.8, dropout=0.2, softmax_t=1.0):
+                 z_ratio=0.8, dropout=0.2, softmax_t=1.0, gat_slope=0.2):
         super().__init__()
         self.trans_fns = nn.ModuleList([nn.Linear(in_channels, out_channels), nn.Linear(in_channels, out_channels)])
         self.comb_fns = nn.ModuleList([nn.Linear(in_channels + out_channels, out_channels),
@@ -183,12 +194,18 @@ class GLASSConv(nn.Module):
         self.softmax_t = float(softmax_t)
         if aggr == "softmax":  # (no other configuration owns the key: their state_dict is unchanged)
             self.t = nn.Parameter(torch.full((1, ), self.softmax_t))
+        self.gat_slope = float(gat_slope)
+        if aggr == "gat":  # (likewise: only this configuration owns the two keys)
+            self.att_src = nn.Parameter(torch.empty(out_channels))
+            self.att_dst = nn.Parameter(torch.empty(out_channels))
+            _reset_gat_att(self)
 
     def reset_parameters(self):
         for lin in list(self.trans_fns) + list(self.comb_fns):
             lin.reset_parameters()
         self.gn.reset_parameters()
         _reset_softmax_t(self)
+        _reset_gat_att(self)
 
     def forward(self, x_, edge_index, edge_weight, mask, out=None, batch=None):
         """`out` (optional, fused path only): a preallocated [N,H] view (a slice of the JK buffer) to write into.
@@ -203,6 +220,8 @@ class GLASSConv(nn.Module):
             agg = lambda m: ops.spmm_rep(self.adj, m, batch.R)
         elif self.aggr == "softmax":
             agg = lambda m: ops.spmm_softmax(self.adj, m, self.t)
+        elif self.aggr == "gat":
+            agg = lambda m: ops.spmm_gat(self.adj, m, self.att_src, self.att_dst, self.gat_slope)
         else:
             agg = lambda m: ops.spmm(self.adj, m)
         rep = {} if batch is None else {"rep": batch}  # (a training pass collects the weight gradients replica by replica)

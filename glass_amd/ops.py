@@ -213,11 +213,60 @@ def spmm_softmax(adj, x, t):
     return SpMMSoftmaxFn.apply(adj, x, t)
 
 
+class SpMMGatFn(torch.autograd.Function):
+    """y[i] = attention-weighted mean of the messages x[col] over the entries of row i of A (aggr "gat", K1a:
+    csrc/spmm_gat.hip): the weights are the softmax, times the edge weights, of LeakyReLU(x[col] . att_src + x[i] . att_dst).
+    One head; multi-head attention (heads > 1) is not built.  The node keeps x, y, the log-sum-exp and the two node scores;
+    the backward runs the edge pass, then the transposed pass only when x needs a gradient and the two column reductions only
+    when an attention vector does (A carries none)."""
+    @staticmethod
+    def forward(ctx, adj, x, att_src, att_dst, slope):
+        _need_gpu(x)
+        x, _ = _rows(x)
+        a, b = adj.gat_scores(x, att_src, att_dst)
+        y, lse = adj.gat_fwd(x, a, b, slope)
+        ctx.adj, ctx.slope = adj, float(slope)
+        ctx.save_for_backward(x, y, lse, a, b, att_src, att_dst)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy, _ = _rows(dy)
+        x, y, lse, a, b, att_src, att_dst = ctx.saved_tensors
+        adj = ctx.adj
+        need_x, need_att = ctx.needs_input_grad[1], ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        if not (need_x or need_att):
+            return None, None, None, None, None
+        g, db = adj.gat_edge(dy, x, y, lse, a, b, ctx.slope)
+        dx = da = ds = dd = None
+        if need_x:
+            dx, da = adj.gat_bwd(dy, lse, a, b, g, db, att_src, att_dst, ctx.slope)
+        if need_att:
+            if da is None:  # the transposed pass's walk for da alone: the same bits, no rows read
+                da = adj.gat_da(g, dy)
+            ds, dd = adj.gat_datt(x, da, db)
+            ds = ds if ctx.needs_input_grad[2] else None
+            dd = dd if ctx.needs_input_grad[3] else None
+        return None, dx, ds, dd, None
+
+
+def spmm_gat(adj, x, att_src, att_dst, slope=0.2):
+    """Attention neighbour aggregation (single-head GAT): `adj` a graph.CSRAdj built for aggr "gat", att_src / att_dst two
+    fp32 vectors of x's width on the device (parameters, or any tensors), slope LeakyReLU's negative slope.  One head only:
+    multi-head attention (heads > 1) is out of scope."""
+    if getattr(adj, "aggr", None) != "gat":
+        raise GlassHipError(f"spmm_gat: the adjacency was built for aggr {getattr(adj, 'aggr', None)!r}, not 'gat'")
+    return SpMMGatFn.apply(adj, x, att_src, att_dst, slope)
+
+
 def spmm(adj, x):
     if getattr(adj, "aggr", None) == "max":
         return SpMMMaxFn.apply(adj, x)
     if getattr(adj, "aggr", None) == "softmax":
         raise GlassHipError("spmm: a softmax adjacency has no temperature of its own; call ops.spmm_softmax(adj, x, t)")
+    if getattr(adj, "aggr", None) == "gat":
+        raise GlassHipError("spmm: a gat adjacency has no attention vectors of its own; call "
+                            "ops.spmm_gat(adj, x, att_src, att_dst, slope)")
     return SpMMFn.apply(adj, x)
 
 
@@ -1034,6 +1083,9 @@ def spmm_rep(adj, x, R):
                             "zero-one labels / --use_zeroone with it)")
     if getattr(adj, "aggr", None) == "softmax":
         raise GlassHipError("replicated softmax aggregation is not built: aggr 'softmax' runs one graph at a time (no exact "
+                            "zero-one labels / --use_zeroone with it)")
+    if getattr(adj, "aggr", None) == "gat":
+        raise GlassHipError("replicated gat aggregation is not built: aggr 'gat' runs one graph at a time (no exact "
                             "zero-one labels / --use_zeroone with it)")
     return SpMMRepFn.apply(adj, x, int(R))
 

@@ -57,7 +57,7 @@ class PairProgram:
         from .models import EdgeGNN, EmbGConv
         if not (isinstance(model, EdgeGNN) and isinstance(model.conv, EmbGConv) and len(model.preds) == 1):
             return False
-        if not stack.StackProgram.supported(model.conv):  # (also: aggr "max" / "softmax" — no fused form, the per-op path serves them)
+        if not stack.StackProgram.supported(model.conv):  # (also: aggr "max" / "softmax" / "gat" — no fused form, the per-op path serves them)
             return False
         hl = _head_layers(model.preds[0])
         if hl is None:

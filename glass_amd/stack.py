@@ -583,9 +583,9 @@ class StackProgram:
     @staticmethod
     def supported(emb):
         from .models import GLASSConv, EmbGConv, _act_code
-        if any(getattr(c, "aggr", None) in ("max", "softmax") for c in emb.convs):
-            # max and softmax aggregation are no products: no fused form, the per-op path (ops.spmm -> K1m,
-            # ops.spmm_softmax -> K1s) serves them
+        if any(getattr(c, "aggr", None) in ("max", "softmax", "gat") for c in emb.convs):
+            # max, softmax and attention aggregation are no products: no fused form, the per-op path (ops.spmm -> K1m,
+            # ops.spmm_softmax -> K1s, ops.spmm_gat -> K1a) serves them
             return False
         if isinstance(emb, EmbGConv):
             return StackProgram.supported_unlabeled(emb)

@@ -182,6 +182,72 @@ int glass_spmm_softmax_dt_f32(const int32_t* rowptr, const int32_t* col, const f
                               int64_t n_rows, int64_t H,
                               const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
 
+/* K1a attention neighbour aggregation (aggr "gat": an extension, the reference has none; single-head GAT) at the call site K1
+ *     serves, on K1's CSR and plans.  Forward CSR as for K1s (raw weights > 0, multiplicities; the caller's check).  att_src,
+ *     att_dst: two [H] fp32 vectors in device memory; slope: LeakyReLU's negative slope, by value.  With
+ *     a[j] = X[j,:] . att_src, b[i] = X[i,:] . att_dst, u_e = a[col[e]] + b[i] (one rounded add) and s_e = u_e > 0 ? u_e :
+ *     slope * u_e (one rounded multiply), for the entries e of row i:
+ *
+ *   glass_gat_scores_f32: a and b ([n_rows] each) from X, sums in fp64 in a fixed order, rounded once.
+ *   glass_spmm_gat_csr_f32: M = max_e s_e, Z = sum_e val[e] exp(s_e - M):  Y[i,:] = (sum_e val[e] exp(s_e - M) X[col[e],:]) / Z,
+ *     L[i] = M + log Z ([n_rows]).  A row without entries: Y = 0, L = 0.  ws: glass_spmm_gat_ws_bytes(hdr, H) = the plan's
+ *     partial slots times (H + 2) floats; cut rows are merged by a second launch in slot order.
+ *   glass_spmm_gat_edge_f32: the sampled dense-dense product of the backward, on the FORWARD CSR, with p_e = val[e] exp(s_e -
+ *     L[i]), f_e = u_e > 0 ? 1 : slope, D_i = dY[i,:] . Y[i,:], q_e = dY[i,:] . X[col[e],:]:  g[e] = p_e (q_e - D_i) f_e for
+ *     every entry ([nnz], forward entry order) and db[i] = sum over the entries of row i of g[e] ([n_rows]; 0 for a row without
+ *     entries).  ws: glass_spmm_gat_edge_ws_bytes(hdr, H) = one float per partial slot.
+ *   glass_spmm_gat_bwd_f32: on the TRANSPOSED CSR (row j = source, col_t = destinations i, val_t, eid_t[t] = the forward index
+ *     of transposed entry t, its own plan): da[j] = sum over the entries of row j of g[eid_t[t]] ([n_rows], written) and
+ *     dX[j,:] = sum over the entries of p dY[i,:]  +  da[j] att_src  +  db[j] att_dst  (p recomputed from a[j], b[i], L[i]); a
+ *     row without entries gets db[j] att_dst.  ws: glass_spmm_gat_bwd_ws_bytes(hdr_t, H) = partial slots times (H + 1) floats.
+ *   glass_spmm_gat_da_f32: da alone, for a backward that trains the attention vectors and needs no dX: the walk of
+ *     glass_spmm_gat_bwd_f32 without its rows and exponentials.  H and vec_form (nonzero: the 16-byte form, H % 4 == 0) name
+ *     the lane layout; da then has the bits glass_spmm_gat_bwd_f32 writes in that form.  ws: glass_spmm_gat_da_ws_bytes(hdr_t,
+ *     H) = one float per partial slot.
+ *   glass_gat_datt_f32: datt_src[c] = sum_j da[j] X[j,c], datt_dst[c] = sum_i db[i] X[i,c]: fp64 partials per workgroup, a
+ *     one-workgroup final stage in workgroup order, each written as fp32.  ws (8-byte aligned): glass_gat_datt_ws_bytes(n_rows,
+ *     H).  n_rows == 0 leaves the outputs untouched.
+ *   All: no float atomics, bitwise repeatable for a given plan; a, b, L, g, db, att_src, att_dst are read when the kernels run
+ *     (a captured launch follows the live parameters).  Every H and leading dimension K1 takes (16-byte vector form when H, the
+ *     ld* and the row pointers allow it, scalar form otherwise).  Refused on the host before any launch: null or misaligned
+ *     pointers, H <= 0, ld* < H, a NaN slope, partial slots without ws -> GLASS_E_ARG; a header that is no plan for n_rows ->
+ *     GLASS_E_PLAN; H beyond 65535 * 64 columns -> GLASS_E_UNSUPPORTED.  n_rows == 0 returns 0 without a launch.  The
+ *     *_ws_bytes queries: GLASS_E_PLAN for a header that is no plan, GLASS_E_ARG for H <= 0 (or n_rows < 0). */
+int glass_gat_scores_f32(const float* X, int64_t ldx, const float* att_src, const float* att_dst,
+                         float* a, float* b,                                             /* [n_rows] each */
+                         int64_t n_rows, int64_t H, void* stream);
+int64_t glass_spmm_gat_ws_bytes(const int32_t* plan_header_host, int64_t H);
+int glass_spmm_gat_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val,  /* CSR of A, device */
+                           const float* X, int64_t ldx,                                  /* [n_cols, H] */
+                           const float* a, const float* b, float slope,
+                           float* Y, int64_t ldy, float* L,                              /* [n_rows, H], [n_rows] */
+                           int64_t n_rows, int64_t H,
+                           const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_spmm_gat_edge_ws_bytes(const int32_t* plan_header_host, int64_t H);
+int glass_spmm_gat_edge_f32(const int32_t* rowptr, const int32_t* col, const float* val, /* CSR of A */
+                            const float* X, int64_t ldx, const float* a, const float* b, float slope,
+                            const float* dY, int64_t lddy, const float* Y, int64_t ldy, const float* L,
+                            float* g, float* db,                                         /* [nnz], [n_rows] */
+                            int64_t n_rows, int64_t H,
+                            const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_spmm_gat_bwd_ws_bytes(const int32_t* plan_t_header_host, int64_t H);
+int glass_spmm_gat_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* val_t, const int32_t* eid_t, /* CSR of A^T */
+                           const float* a, const float* b, float slope,
+                           const float* dY, int64_t lddy, const float* L, const float* g, const float* db,
+                           const float* att_src, const float* att_dst,
+                           float* dX, int64_t lddx, float* da,                           /* [n_rows, H], [n_rows] */
+                           int64_t n_rows, int64_t H,
+                           const int32_t* plan_t_header_host, const int32_t* plan_t_dev, void* ws, void* stream);
+int64_t glass_spmm_gat_da_ws_bytes(const int32_t* plan_t_header_host, int64_t H);
+int glass_spmm_gat_da_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* val_t, const int32_t* eid_t, /* CSR of A^T */
+                          const float* g, float* da,                                     /* [nnz], [n_rows] */
+                          int64_t n_rows, int64_t H, int vec_form,
+                          const int32_t* plan_t_header_host, const int32_t* plan_t_dev, void* ws, void* stream);
+int64_t glass_gat_datt_ws_bytes(int64_t n_rows, int64_t H);
+int glass_gat_datt_f32(const float* X, int64_t ldx, const float* da, const float* db,
+                       float* datt_src, float* datt_dst,                                 /* [H] each */
+                       int64_t n_rows, int64_t H, void* ws, void* stream);
+
 /* K2  normalised edge values of buildAdj (impl/models.py:83-111) on an (row,col)-sorted COO:
  *     deg = segment-sum of w per row, deg<0.5 -> +1; aggr 0=mean w/deg[row], 1=sum w,
  *     2=gcn deg[row]^-1/2 * w * deg[col]^-1/2.  Duplicate (row,col) entries stay separate CSR
