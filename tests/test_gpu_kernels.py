@@ -1450,9 +1450,10 @@ def test_spmm_full_size_properties(shape):
 
 @pytest.mark.parametrize("H", [8, 64, 128, 17])
 def test_spmm_row_parallel_mode_for_short_rows(H):
-    """Short rows (mean degree <= 4 G, G = 64 / lanes-per-row): the sweep kernel's flat mode — indices staged in LDS,
-    every lane group walks its own run of rows as one edge stream.  Degrees 0-3 with a few long rows (>= 256 edges,
-    which belong to the workgroup kernel and cut the sweep items) mixed in."""
+    """Short rows in the sweep kernel's ROW mode: degrees 0-3 with two long rows (300 edges, which belong to the workgroup
+    items and cut the sweep items) mixed in.  The plan holds about 2 500 sweep items, fewer than the 8 192 at which a launch
+    takes the flat-capable build (asserted from the header; tests/test_k1_sum_host.py rebuilds this plan on the host), so
+    every item runs one row at a time.  Flat mode at a small shape is tests/test_gpu_k1_sum.py::test_flat_build's."""
     from glass_amd.graph import CSRAdj
     rng = np.random.default_rng(H)
     n = 6000
@@ -1466,6 +1467,9 @@ def test_spmm_row_parallel_mode_for_short_rows(H):
     x = torch.randn(n, H, generator=torch.Generator().manual_seed(H))
     ref = O.build_adj(ei, ew, n, "sum").to(torch.float64) @ x.double()
     adj = CSRAdj(ei.to(DEV), ew.to(DEV), n, "sum")
+    for h in (adj.fwd.header, adj.bwd.header):  # header word 4: sweep items -> the row-only sweep build at every width
+        assert 0 < int(h[4]) < 8192
+    assert int(adj.fwd.header[5]) == 2 and int(adj.fwd.header[8]) == 64  # the two long rows are workgroup items
     y = adj.fwd.spmm(x.to(DEV))
     assert rel_inf(y.cpu(), ref) < TOL
     assert torch.equal(adj.fwd.spmm(x.to(DEV)), y)
