@@ -55,12 +55,17 @@ def parse_args(argv=None):
     p.add_argument("--aggr", type=str, default=None, choices=("mean", "sum", "gcn", "max", "softmax", "gat"),
                    help="(extension) neighbour aggregation instead of the config file's `aggr` (default: the config's value); "
                         "max: the largest weighted neighbour message per channel; softmax: the softmax-weighted mean of the "
-                        "messages with a learned temperature per layer (positive edge weights); gat: single-head attention, "
+                        "messages with a learned temperature per layer (positive edge weights); gat: attention (--gat_heads heads), "
                         "the weights from two learned vectors per layer (positive edge weights); none of the three is available "
                         "with --use_zeroone")
     p.add_argument("--gat_slope", type=float, default=0.2,
                    help="(extension) LeakyReLU's negative slope in the attention scores of --aggr gat (default: 0.2)")
+    p.add_argument("--gat_heads", type=int, default=1,
+                   help="(extension) attention heads of --aggr gat: they partition the hidden channels, so the count must divide "
+                        "hidden_dim and leave a power of two in [4, 256] channels per head (default: 1)")
     args = p.parse_args(argv)
+    if args.gat_heads < 1:
+        p.error("--gat_heads must be an integer >= 1")
     if args.use_zeroone and args.use_maxzeroone:
         p.error("--use_zeroone and --use_maxzeroone are mutually exclusive")
     if args.clip is not None and not args.clip > 0:
@@ -136,7 +141,7 @@ class Run:
                 SubGDataset.GDataloader(self.val, batch_size, shuffle=True, drop_last=False),
                 SubGDataset.GDataloader(self.tst, batch_size, shuffle=True, drop_last=False))
 
-    def build_model(self, hidden_dim, conv_layer, dropout, jk, pool, z_ratio, aggr):
+    def build_model(self, hidden_dim, conv_layer, dropout, jk, pool, z_ratio, aggr, gat_heads=None):
         a = self.args
         if pool not in POOLS:
             raise NotImplementedError
@@ -145,7 +150,8 @@ class Run:
             conv = models.EmbZGConv(h, h, conv_layer, max_deg=self.max_deg,
                                     activation=nn.ELU(inplace=True), jk=jk, dropout=dropout,
                                     conv=functools.partial(models.GLASSConv, aggr=aggr, z_ratio=z_ratio, dropout=dropout,
-                                                           gat_slope=getattr(a, "gat_slope", 0.2)),
+                                                           gat_slope=getattr(a, "gat_slope", 0.2),
+                                                           gat_heads=getattr(a, "gat_heads", 1) if gat_heads is None else gat_heads),
                                     gn=True)
             if a.use_nodeid:
                 print("load ", f"./Emb/{a.dataset}_{hidden_dim}.pt")
@@ -197,8 +203,9 @@ class Run:
         return epoch + 1, seconds, policy.best_val, policy.test_at_best
 
     def test(self, pool="size", aggr="mean", hidden_dim=64, conv_layer=8, dropout=0.3, jk=1, lr=1e-3, z_ratio=0.8,
-             batch_size=None, resi=0.7):
-        """Train `repeat` times with one hyper-parameter set (the YAML keys); prints the reference's log lines."""
+             batch_size=None, resi=0.7, gat_heads=None):
+        """Train `repeat` times with one hyper-parameter set (the YAML keys); prints the reference's log lines.  gat_heads (an
+        extension key, aggr "gat" only): the attention heads; absent, --gat_heads."""
         # evaluation cadence: both the warm-up and the patience are 100 test-set batches' worth of epochs (synthetic
         # sets: a fifth of that)
         batches_in_test = self.tst.y.shape[0] / batch_size
@@ -210,7 +217,7 @@ class Run:
             set_seed((1 << repeat) - 1)
             print(f"repeat {repeat}")
             self.split()
-            model = self.build_model(hidden_dim, conv_layer, dropout, jk, pool, z_ratio, aggr)
+            model = self.build_model(hidden_dim, conv_layer, dropout, jk, pool, z_ratio, aggr, gat_heads)
             optimizer = Adam(model.parameters(), lr=lr)  # (impl.train.train runs it as one fused launch inside the step's graph)
             if self.args.clip is not None:
                 # torch keeps unknown group keys; the step reads this one (norm launch + clipped Adam inside the step's graph)
@@ -265,6 +272,8 @@ def main(argv=None):
         params["pool"] = args.pool
     if args.aggr is not None:
         params["aggr"] = args.aggr
+    if args.gat_heads != 1:  # (the flag, where given, instead of the config file's `gat_heads`)
+        params["gat_heads"] = args.gat_heads
     run.split()
     return run.test(**params)
 

@@ -94,6 +94,20 @@ SIGNATURES = {
     "glass_spmm_gat_da_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, c_int, _P, _P, _P, _P]),
     "glass_gat_datt_ws_bytes": (c_int64, [_I, _I]),
     "glass_gat_datt_f32": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
+    # (multi-head: the single-head signatures with K after H)
+    "glass_gat_scores_mh_f32": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "glass_spmm_gat_mh_ws_bytes": (c_int64, [_P, _I, _I]),
+    "glass_spmm_gat_mh_csr_f32": (c_int, [_P, _P, _P, _P, _I, _P, _P, c_float, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "glass_spmm_gat_mh_edge_ws_bytes": (c_int64, [_P, _I, _I]),
+    "glass_spmm_gat_mh_edge_f32": (c_int, [_P, _P, _P, _P, _I, _P, _P, c_float, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P,
+                                           _P]),
+    "glass_spmm_gat_mh_bwd_ws_bytes": (c_int64, [_P, _I, _I]),
+    "glass_spmm_gat_mh_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P,
+                                          _P, _P]),
+    "glass_spmm_gat_mh_da_ws_bytes": (c_int64, [_P, _I, _I]),
+    "glass_spmm_gat_mh_da_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, c_int, _P, _P, _P, _P]),
+    "glass_gat_datt_mh_ws_bytes": (c_int64, [_I, _I]),
+    "glass_gat_datt_mh_f32": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "glass_adj_values_f32": (c_int, [_P, _P, _P, _I, c_int, _P, _P, _P]),
     "glass_maxzoz_i64": (c_int, [_P, _I, _P, _I, _P]),
     "glass_embed_label_f32": (c_int, [_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _P]),

@@ -21,21 +21,9 @@
 // one-workgroup final stage.  Lane groups (__shfl_xor), the four waves of a long-row item (LDS) and the chunks of a cut row
 // (workspace partials, a small second launch, slot order) combine in a fixed order: no float atomics, every entry bitwise
 // repeatable for a given plan.  a, b, L, g, db, att_src and att_dst are read from device memory when the kernels run.
-#include "spmm_items.h"
+#include "spmm_gat_common.h"
 
 namespace glass {
-
-constexpr int kGatFwdGathers = kGathers;  // U of the forward: one row and one score per entry in flight, as K1
-constexpr int kGatEdgeGathers = 4;        // U of the edge pass: one row per entry, the row's dY beside it
-constexpr int kGatBwdGathers = 4;         // U of the transposed pass: one row and three scalars per entry
-constexpr int kScoreRows = kBlock / kWave;  // node scores: one wave per row
-
-// the score of one entry from its source's a and its destination's b, the same bits in all three passes
-__device__ __forceinline__ float gat_score(float a, float b, float slope) {
-    const float u = __fadd_rn(a, b);
-    return u > 0.f ? u : __fmul_rn(slope, u);
-}
-__device__ __forceinline__ float gat_slope_of(float a, float b, float slope) { return __fadd_rn(a, b) > 0.f ? 1.f : slope; }
 
 // ---- node scores: a = X att_src, b = X att_dst ------------------------------------------------------------------------------
 // one wave per row; lane l sums columns l, l + 64, ... in fp64, then the lanes in a butterfly: a fixed order
@@ -61,70 +49,6 @@ __global__ __launch_bounds__(kBlock) void gat_scores_kernel(const float* __restr
     }
 }
 
-// ---- the forward's state: one online-softmax pair (M, Z), the same on every lane of a row, and VW running sums ---------------
-template <int VW>
-struct GatAcc {
-    float m, z, s[VW];
-    static constexpr int kLdsWords = VW + 2;
-    __device__ __forceinline__ void init() {
-        m = -INFINITY;
-        z = 0.f;
-#pragma unroll
-        for (int k = 0; k < VW; ++k) s[k] = 0.f;
-    }
-    // one entry with weight v > 0, score sc (finite), message row x: ONE exponential, exp(-|sc - M|), which rescales either
-    // the running sums or the entry (SmTriple's rule)
-    __device__ __forceinline__ void take(bool ok, float v, float sc, const float (&x)[VW]) {
-        const float d = sc - m;  // +inf on the first entry: e = 0, the empty sums are dropped
-        const float e = expf(-fabsf(d));
-        const bool up = d > 0.f;
-        const float f = up ? e : 1.f;
-        const float w = up ? v : v * e;
-        const float zn = fmaf(z, f, w);
-#pragma unroll
-        for (int k = 0; k < VW; ++k) {
-            const float sn = fmaf(s[k], f, w * x[k]);
-            s[k] = ok ? sn : s[k];
-        }
-        m = (ok && up) ? sc : m;
-        z = ok ? zn : z;
-    }
-    // another partial of the same row (either may be empty: m = -inf, z = s = 0)
-    __device__ __forceinline__ void merge(float om, float oz, const float (&os)[VW]) {
-        const float nm = fmaxf(m, om);
-        const float a = (m == nm) ? 1.f : expf(m - nm);
-        const float b = (om == nm) ? 1.f : expf(om - nm);
-        z = fmaf(z, a, oz * b);
-#pragma unroll
-        for (int k = 0; k < VW; ++k) s[k] = fmaf(s[k], a, os[k] * b);
-        m = nm;
-    }
-    __device__ __forceinline__ void xor_merge(int sh) {
-        const float om = __shfl_xor(m, sh), oz = __shfl_xor(z, sh);
-        float os[VW];
-#pragma unroll
-        for (int k = 0; k < VW; ++k) os[k] = __shfl_xor(s[k], sh);
-        merge(om, oz, os);
-    }
-    __device__ __forceinline__ void to_lds(int32_t* p) const {
-        p[0] = __float_as_int(m);
-        p[1] = __float_as_int(z);
-#pragma unroll
-        for (int k = 0; k < VW; ++k) p[2 + k] = __float_as_int(s[k]);
-    }
-    __device__ __forceinline__ void from_lds(const int32_t* p) {
-        m = __int_as_float(p[0]);
-        z = __int_as_float(p[1]);
-#pragma unroll
-        for (int k = 0; k < VW; ++k) s[k] = __int_as_float(p[2 + k]);
-    }
-    __device__ __forceinline__ void merge_lds(const int32_t* p) {
-        float os[VW];
-#pragma unroll
-        for (int k = 0; k < VW; ++k) os[k] = __int_as_float(p[2 + k]);
-        merge(__int_as_float(p[0]), __int_as_float(p[1]), os);
-    }
-};
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------
 template <int VW_, int LPR_>
@@ -314,37 +238,6 @@ __global__ __launch_bounds__(kBlock) void spmm_gat_edge_reduce_kernel(const floa
 }
 
 // ---- transposed pass: row j of A^T; per entry the destination's dY row, b, L and the entry's g (through eid_t) -----------------
-template <int VW>
-struct GatBwdAcc {
-    float da, s[VW];
-    static constexpr int kLdsWords = VW + 1;
-    __device__ __forceinline__ void init() {
-        da = 0.f;
-#pragma unroll
-        for (int k = 0; k < VW; ++k) s[k] = 0.f;
-    }
-    __device__ __forceinline__ void xor_merge(int sh) {
-        da += __shfl_xor(da, sh);
-#pragma unroll
-        for (int k = 0; k < VW; ++k) s[k] += __shfl_xor(s[k], sh);
-    }
-    __device__ __forceinline__ void to_lds(int32_t* p) const {
-        p[0] = __float_as_int(da);
-#pragma unroll
-        for (int k = 0; k < VW; ++k) p[1 + k] = __float_as_int(s[k]);
-    }
-    __device__ __forceinline__ void from_lds(const int32_t* p) {
-        da = __int_as_float(p[0]);
-#pragma unroll
-        for (int k = 0; k < VW; ++k) s[k] = __int_as_float(p[1 + k]);
-    }
-    __device__ __forceinline__ void merge_lds(const int32_t* p) {
-        da += __int_as_float(p[0]);
-#pragma unroll
-        for (int k = 0; k < VW; ++k) s[k] += __int_as_float(p[1 + k]);
-    }
-};
-
 // DX = false is the same walk for da alone (glass_spmm_gat_da_f32: the attention vectors are trained, X needs no gradient):
 // one column tile, no dY row, no exponential — and, entry for entry, the additions of the full pass at this lane layout, so
 // da has the same bits either way.

@@ -134,7 +134,8 @@ class CSRAdj:
     edge weights (the values of "sum"), aggregated by K1m (max_fwd / max_bwd) instead of K1's product.  aggr "softmax" (an
     extension): the raw weights too, strictly positive (checked here, once), aggregated by K1s (softmax_fwd / softmax_bwd /
     softmax_dt) with a temperature the caller owns.  aggr "gat" (an extension): built like "softmax", aggregated by K1a
-    (gat_scores / gat_fwd / gat_edge / gat_bwd / gat_datt) with two attention vectors the caller owns."""
+    (gat_scores / gat_fwd / gat_edge / gat_bwd / gat_datt, each with heads=K for multi-head attention) with two attention
+    vectors the caller owns."""
     def __init__(self, edge_index, edge_weight, n_node, aggr):
         if aggr not in _lib.AGGR_MODES and aggr not in ("max", "softmax", "gat"):
             raise NotImplementedError  # same error type as the reference (models.py:110-111)
@@ -312,11 +313,43 @@ class CSRAdj:
             f"{name}: {n} contiguous fp32 on the device"
         return v.data_ptr()  # read by the kernels when they run: a captured launch follows the parameter
 
-    def gat_scores(self, x, att_src, att_dst):
-        """(a, b) = K1a node scores: a = x @ att_src, b = x @ att_dst, [N] each (fp64 sums, rounded once)."""
+    @staticmethod
+    def gat_head_width(H, heads):
+        """D = H / heads where the multi-head kernels serve it (heads divides H, D a power of two in [4, 256]; heads == 1: any
+        H); ValueError otherwise."""
+        H, K = int(H), int(heads)
+        if K < 1:
+            raise ValueError(f"gat: heads must be an integer >= 1, not {heads!r}")
+        if K == 1:
+            return H
+        D = H // K
+        if H % K != 0 or D < 4 or D > 256 or D & (D - 1):
+            raise ValueError(f"gat: {K} heads over {H} channels (D = {H / K:g}) is not supported: heads must divide the width "
+                             "and D = width / heads be a power of two in [4, 256]")
+        return D
+
+    def _gat_mat(self, v, n, K, name):
+        """an [n, K] temporary of the multi-head kernels, row-major"""
+        assert v.shape == (n, K) and v.is_contiguous() and v.dtype == torch.float32 and v.is_cuda, \
+            f"{name}: [{n}, {K}] contiguous fp32 on the device"
+        return v.data_ptr()
+
+    def gat_scores(self, x, att_src, att_dst, heads=1):
+        """(a, b) = K1a node scores: a = x @ att_src, b = x @ att_dst, [N] each (fp64 sums, rounded once).  heads = K > 1: per
+        head, over the head's columns, [N, K] each (here and below: the glass_*_mh_* entries, csrc/spmm_gat_mh.hip)."""
         self._need_gat("gat_scores")
         ldx = self._softmax_operand(x, self.n_node, "X")
         H = x.shape[1]
+        if heads != 1:
+            K = int(heads)
+            self.gat_head_width(H, K)
+            a = torch.empty((self.n_node, K), dtype=torch.float32, device=x.device)
+            b = torch.empty((self.n_node, K), dtype=torch.float32, device=x.device)
+            rc = _lib.load().glass_gat_scores_mh_f32(x.data_ptr(), ldx, self._gat_vec(att_src, H, "att_src"),
+                                                     self._gat_vec(att_dst, H, "att_dst"), a.data_ptr(), b.data_ptr(), self.n_node,
+                                                     H, K, torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "glass_gat_scores_mh_f32")
+            return a, b
         a = torch.empty(self.n_node, dtype=torch.float32, device=x.device)
         b = torch.empty(self.n_node, dtype=torch.float32, device=x.device)
         rc = _lib.load().glass_gat_scores_f32(x.data_ptr(), ldx, self._gat_vec(att_src, H, "att_src"),
@@ -325,7 +358,7 @@ class CSRAdj:
         _lib.check(rc, "glass_gat_scores_f32")
         return a, b
 
-    def gat_fwd(self, x, a, b, slope):
+    def gat_fwd(self, x, a, b, slope, heads=1):
         """(y, lse) = K1a forward: per destination the attention-weighted mean of the neighbour messages, the weights a softmax
         over the row's entries of LeakyReLU(a[source] + b[destination]); lse [N] = max + log of the weighted sum of
         exponentials, kept for the backward."""
@@ -335,6 +368,18 @@ class CSRAdj:
         H = x.shape[1]
         lib = _lib.load()
         y = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
+        if heads != 1:  # lse [N, K]
+            K = int(heads)
+            self.gat_head_width(H, K)
+            lse = torch.empty((op.n_rows, K), dtype=torch.float32, device=x.device)
+            ws = self._aggr_workspace("gat_fwd", (H, K), lib.glass_spmm_gat_mh_ws_bytes(op.header.ctypes.data, H, K))
+            rc = lib.glass_spmm_gat_mh_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
+                                               self._gat_mat(a, op.n_cols, K, "a"), self._gat_mat(b, op.n_rows, K, "b"),
+                                               float(slope), y.data_ptr(), H, lse.data_ptr(), op.n_rows, H, K,
+                                               op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
+                                               torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "glass_spmm_gat_mh_csr_f32")
+            return y, lse
         lse = torch.empty(op.n_rows, dtype=torch.float32, device=x.device)
         ws = self._aggr_workspace("gat_fwd", H, lib.glass_spmm_gat_ws_bytes(op.header.ctypes.data, H))
         rc = lib.glass_spmm_gat_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
@@ -344,7 +389,7 @@ class CSRAdj:
         _lib.check(rc, "glass_spmm_gat_csr_f32")
         return y, lse
 
-    def gat_edge(self, dy, x, y, lse, a, b, slope):
+    def gat_edge(self, dy, x, y, lse, a, b, slope, heads=1):
         """(g, db) = K1a edge pass over the forward CSR: g [nnz] the score gradient of every entry, in forward entry order (a
         sampled dense-dense product: per entry the dot of dy[destination] and x[source]), db [N] its row sums."""
         self._need_gat("gat_edge")
@@ -354,6 +399,20 @@ class CSRAdj:
         assert dy.shape == x.shape == y.shape
         H = x.shape[1]
         lib = _lib.load()
+        if heads != 1:  # g [nnz, K], db [N, K]
+            K = int(heads)
+            self.gat_head_width(H, K)
+            g = torch.empty((max(op.nnz, 1), K), dtype=torch.float32, device=x.device)[:op.nnz]
+            db = torch.empty((op.n_rows, K), dtype=torch.float32, device=x.device)
+            ws = self._aggr_workspace("gat_edge", (H, K), lib.glass_spmm_gat_mh_edge_ws_bytes(op.header.ctypes.data, H, K))
+            rc = lib.glass_spmm_gat_mh_edge_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
+                                                self._gat_mat(a, op.n_cols, K, "a"), self._gat_mat(b, op.n_rows, K, "b"),
+                                                float(slope), dy.data_ptr(), lddy, y.data_ptr(), ldy,
+                                                self._gat_mat(lse, op.n_rows, K, "L"), g.data_ptr(), db.data_ptr(), op.n_rows, H, K,
+                                                op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
+                                                torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "glass_spmm_gat_mh_edge_f32")
+            return g, db
         g = torch.empty(max(op.nnz, 1), dtype=torch.float32, device=x.device)[:op.nnz]
         db = torch.empty(op.n_rows, dtype=torch.float32, device=x.device)
         ws = self._aggr_workspace("gat_edge", H, lib.glass_spmm_gat_edge_ws_bytes(op.header.ctypes.data, H))
@@ -365,7 +424,7 @@ class CSRAdj:
         _lib.check(rc, "glass_spmm_gat_edge_f32")
         return g, db
 
-    def gat_bwd(self, dy, lse, a, b, g, db, att_src, att_dst, slope):
+    def gat_bwd(self, dy, lse, a, b, g, db, att_src, att_dst, slope, heads=1):
         """(dx, da) = K1a transposed pass: dx[j] = the attention-weighted sum of dy over the entries that read x[j], plus
         da[j] att_src + db[j] att_dst; da [N] = the sums of g over those entries."""
         self._need_gat("gat_bwd")
@@ -374,6 +433,20 @@ class CSRAdj:
         H = dy.shape[1]
         lib = _lib.load()
         dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=dy.device)
+        if heads != 1:  # da [N, K]
+            K = int(heads)
+            self.gat_head_width(H, K)
+            da = torch.empty((op.n_rows, K), dtype=torch.float32, device=dy.device)
+            ws = self._aggr_workspace("gat_bwd", (H, K), lib.glass_spmm_gat_mh_bwd_ws_bytes(op.header.ctypes.data, H, K))
+            rc = lib.glass_spmm_gat_mh_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
+                                               self._gat_mat(a, op.n_rows, K, "a"), self._gat_mat(b, op.n_cols, K, "b"),
+                                               float(slope), dy.data_ptr(), lddy, self._gat_mat(lse, op.n_cols, K, "L"),
+                                               self._gat_mat(g, op.nnz, K, "g"), self._gat_mat(db, op.n_rows, K, "db"),
+                                               self._gat_vec(att_src, H, "att_src"), self._gat_vec(att_dst, H, "att_dst"),
+                                               dx.data_ptr(), H, da.data_ptr(), op.n_rows, H, K, op.header.ctypes.data,
+                                               op.plan.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "glass_spmm_gat_mh_bwd_f32")
+            return dx, da
         da = torch.empty(op.n_rows, dtype=torch.float32, device=dy.device)
         assert g.dtype == torch.float32 and g.shape == (op.nnz, ) and g.stride(0) == 1
         ws = self._aggr_workspace("gat_bwd", H, lib.glass_spmm_gat_bwd_ws_bytes(op.header.ctypes.data, H))
@@ -387,7 +460,7 @@ class CSRAdj:
         _lib.check(rc, "glass_spmm_gat_bwd_f32")
         return dx, da
 
-    def gat_da(self, g, dy):
+    def gat_da(self, g, dy, heads=1):
         """da alone (gat_bwd's second result, the same bits) when no dx is wanted; dy only names the lane layout gat_bwd would
         take (its width, stride and alignment)."""
         self._need_gat("gat_da")
@@ -395,6 +468,18 @@ class CSRAdj:
         lddy = self._softmax_operand(dy, op.n_cols, "dY")
         H = dy.shape[1]
         lib = _lib.load()
+        if heads != 1:
+            K = int(heads)
+            self.gat_head_width(H, K)
+            da = torch.empty((op.n_rows, K), dtype=torch.float32, device=g.device)
+            ws = self._aggr_workspace("gat_da", (H, K), lib.glass_spmm_gat_mh_da_ws_bytes(op.header.ctypes.data, H, K))
+            vec = lddy % 4 == 0 and dy.data_ptr() % 16 == 0  # (gat_bwd's own dx and workspace are 16-byte aligned)
+            rc = lib.glass_spmm_gat_mh_da_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
+                                              self._gat_mat(g, op.nnz, K, "g"), da.data_ptr(), op.n_rows, H, K, int(vec),
+                                              op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
+                                              torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "glass_spmm_gat_mh_da_f32")
+            return da
         da = torch.empty(op.n_rows, dtype=torch.float32, device=g.device)
         assert g.dtype == torch.float32 and g.shape == (op.nnz, ) and g.stride(0) == 1
         ws = self._aggr_workspace("gat_da", H, lib.glass_spmm_gat_da_ws_bytes(op.header.ctypes.data, H))
@@ -405,7 +490,7 @@ class CSRAdj:
         _lib.check(rc, "glass_spmm_gat_da_f32")
         return da
 
-    def gat_datt(self, x, da, db):
+    def gat_datt(self, x, da, db, heads=1):
         """(datt_src, datt_dst) = x^T da, x^T db: the attention vectors' gradients, run only when they are trained."""
         self._need_gat("gat_datt")
         ldx = self._softmax_operand(x, self.n_node, "X")
@@ -413,6 +498,15 @@ class CSRAdj:
         lib = _lib.load()
         ds = torch.zeros(H, dtype=torch.float32, device=x.device)
         dd = torch.zeros(H, dtype=torch.float32, device=x.device)
+        if heads != 1:
+            K = int(heads)
+            self.gat_head_width(H, K)
+            ws = self._aggr_workspace("gat_datt", (H, K), lib.glass_gat_datt_mh_ws_bytes(self.n_node, H))
+            rc = lib.glass_gat_datt_mh_f32(x.data_ptr(), ldx, self._gat_mat(da, self.n_node, K, "da"),
+                                           self._gat_mat(db, self.n_node, K, "db"), ds.data_ptr(), dd.data_ptr(), self.n_node, H, K,
+                                           ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "glass_gat_datt_mh_f32")
+            return ds, dd
         ws = self._aggr_workspace("gat_datt", H, lib.glass_gat_datt_ws_bytes(self.n_node, H))
         rc = lib.glass_gat_datt_f32(x.data_ptr(), ldx, self._gat_vec(da, self.n_node, "da"), self._gat_vec(db, self.n_node, "db"),
                                     ds.data_ptr(), dd.data_ptr(), self.n_node, H, ws.data_ptr(),

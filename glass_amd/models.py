@@ -8,9 +8,11 @@ Reference map (file:line under /root/reference):
   Seq 10-24 · MLP 27-80 · buildAdj 83-111 · GLASSConv 114-174 · EmbZGConv 177-272 ·
   PoolModule/AddPool/MaxPool/MeanPool/SizePool 275-319 · GLASS 322-355   (impl/models.py)
 Not in the reference: AttnPool (attention readout, pool "attn"); aggr "max" (max neighbour aggregation, buildAdj); aggr
-"softmax" (softmax neighbour aggregation with a learned temperature: the conv layers' parameter `t`); aggr "gat" (single-head
-attention aggregation: GLASSConv's parameters `att_src` and `att_dst`).
+"softmax" (softmax neighbour aggregation with a learned temperature: the conv layers' parameter `t`); aggr "gat" (attention
+aggregation with `gat_heads` heads: GLASSConv's parameters `att_src` and `att_dst`).
 """
+import math
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -166,20 +168,25 @@ def _reset_softmax_t(conv):
 
 
 def _reset_gat_att(conv):
-    """The attention vectors of a conv layer with aggr "gat": xavier_uniform_ on their [1, H] views (in place)."""
+    """The attention vectors of a conv layer with aggr "gat": xavier_uniform_ on the [1, D] view of every head, D = H /
+    gat_heads (in place): one uniform_ call per vector with the bound sqrt(6 / (1 + D)) — at one head, xavier_uniform_ on the
+    [1, H] view, draw for draw."""
     if conv.aggr == "gat":
+        bound = math.sqrt(3.0) * math.sqrt(2.0 / float(1 + conv.att_src.numel() // conv.gat_heads))  # (xavier_uniform_'s own arithmetic)
         with torch.no_grad():
-            nn.init.xavier_uniform_(conv.att_src.view(1, -1))
-            nn.init.xavier_uniform_(conv.att_dst.view(1, -1))
+            conv.att_src.uniform_(-bound, bound)
+            conv.att_dst.uniform_(-bound, bound)
 
 
 class GLASSConv(nn.Module):
     """Labeled message-passing layer: two weight sets (index 1 = labeled, 0 = unlabeled) mixed by
-    z_ratio before and after the neighbour aggregation.  aggr "gat" (an extension): single-head attention over the mixed
-    messages, the layer owns att_src and att_dst ([out_channels] each) and the constant gat_slope (LeakyReLU's negative
-    slope); multi-head attention (heads > 1) is out of scope."""
+    z_ratio before and after the neighbour aggregation.  aggr "gat" (an extension): attention over the mixed messages, the
+    layer owns att_src and att_dst ([out_channels] each) and the constants gat_slope (LeakyReLU's negative slope) and
+    gat_heads: K heads partition the channels (head h: channels [h D, (h + 1) D), D = out_channels / K, of the messages, the
+    result and both vectors), each with its own softmax; the output width and the state_dict do not depend on K.  K must
+    divide out_channels and D be a power of two in [4, 256] (ValueError at construction; other aggregations ignore it)."""
     def __init__(self, in_channels: int, out_channels: int, activation=nn.ReLU(inplace=True), aggr="mean",
-                 z_ratio=0.8, dropout=0.2, softmax_t=1.0, gat_slope=0.2):
+                 z_ratio=0.8, dropout=0.2, softmax_t=1.0, gat_slope=0.2, gat_heads=1):
         super().__init__()
         self.trans_fns = nn.ModuleList([nn.Linear(in_channels, out_channels), nn.Linear(in_channels, out_channels)])
         self.comb_fns = nn.ModuleList([nn.Linear(in_channels + out_channels, out_channels),
@@ -195,7 +202,13 @@ class GLASSConv(nn.Module):
         if aggr == "softmax":  # (no other configuration owns the key: their state_dict is unchanged)
             self.t = nn.Parameter(torch.full((1, ), self.softmax_t))
         self.gat_slope = float(gat_slope)
+        self.gat_heads = gat_heads
         if aggr == "gat":  # (likewise: only this configuration owns the two keys)
+            if isinstance(gat_heads, bool) or int(gat_heads) != gat_heads:
+                raise ValueError(f"GLASSConv: gat_heads must be an integer >= 1, not {gat_heads!r}")
+            self.gat_heads = int(gat_heads)
+            from .graph import CSRAdj
+            CSRAdj.gat_head_width(out_channels, self.gat_heads)
             self.att_src = nn.Parameter(torch.empty(out_channels))
             self.att_dst = nn.Parameter(torch.empty(out_channels))
             _reset_gat_att(self)
@@ -221,7 +234,7 @@ class GLASSConv(nn.Module):
         elif self.aggr == "softmax":
             agg = lambda m: ops.spmm_softmax(self.adj, m, self.t)
         elif self.aggr == "gat":
-            agg = lambda m: ops.spmm_gat(self.adj, m, self.att_src, self.att_dst, self.gat_slope)
+            agg = lambda m: ops.spmm_gat(self.adj, m, self.att_src, self.att_dst, self.gat_slope, self.gat_heads)
         else:
             agg = lambda m: ops.spmm(self.adj, m)
         rep = {} if batch is None else {"rep": batch}  # (a training pass collects the weight gradients replica by replica)

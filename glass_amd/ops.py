@@ -213,19 +213,26 @@ def spmm_softmax(adj, x, t):
     return SpMMSoftmaxFn.apply(adj, x, t)
 
 
+def _heads_kw(heads):
+    """heads == 1 calls the CSRAdj methods exactly as before the argument existed"""
+    return {} if heads == 1 else {"heads": heads}
+
+
 class SpMMGatFn(torch.autograd.Function):
     """y[i] = attention-weighted mean of the messages x[col] over the entries of row i of A (aggr "gat", K1a:
     csrc/spmm_gat.hip): the weights are the softmax, times the edge weights, of LeakyReLU(x[col] . att_src + x[i] . att_dst).
-    One head; multi-head attention (heads > 1) is not built.  The node keeps x, y, the log-sum-exp and the two node scores;
-    the backward runs the edge pass, then the transposed pass only when x needs a gradient and the two column reductions only
-    when an attention vector does (A carries none)."""
+    heads = K > 1 (csrc/spmm_gat_mh.hip): K heads partition the channels, head h owns columns [h D, (h + 1) D) of x, y and the
+    two vectors, D = H / K, and has its own softmax; the scores and the log-sum-exp are then [N, K].  The node keeps x, y, the
+    log-sum-exp and the two node scores; the backward runs the edge pass, then the transposed pass only when x needs a
+    gradient and the two column reductions only when an attention vector does (A carries none)."""
     @staticmethod
-    def forward(ctx, adj, x, att_src, att_dst, slope):
+    def forward(ctx, adj, x, att_src, att_dst, slope, heads):
         _need_gpu(x)
         x, _ = _rows(x)
-        a, b = adj.gat_scores(x, att_src, att_dst)
-        y, lse = adj.gat_fwd(x, a, b, slope)
-        ctx.adj, ctx.slope = adj, float(slope)
+        heads = int(heads)
+        a, b = adj.gat_scores(x, att_src, att_dst, **_heads_kw(heads))
+        y, lse = adj.gat_fwd(x, a, b, slope, **_heads_kw(heads))
+        ctx.adj, ctx.slope, ctx.heads = adj, float(slope), heads
         ctx.save_for_backward(x, y, lse, a, b, att_src, att_dst)
         return y
 
@@ -236,27 +243,35 @@ class SpMMGatFn(torch.autograd.Function):
         adj = ctx.adj
         need_x, need_att = ctx.needs_input_grad[1], ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
         if not (need_x or need_att):
-            return None, None, None, None, None
-        g, db = adj.gat_edge(dy, x, y, lse, a, b, ctx.slope)
+            return None, None, None, None, None, None
+        kw = _heads_kw(ctx.heads)
+        g, db = adj.gat_edge(dy, x, y, lse, a, b, ctx.slope, **kw)
         dx = da = ds = dd = None
         if need_x:
-            dx, da = adj.gat_bwd(dy, lse, a, b, g, db, att_src, att_dst, ctx.slope)
+            dx, da = adj.gat_bwd(dy, lse, a, b, g, db, att_src, att_dst, ctx.slope, **kw)
         if need_att:
             if da is None:  # the transposed pass's walk for da alone: the same bits, no rows read
-                da = adj.gat_da(g, dy)
-            ds, dd = adj.gat_datt(x, da, db)
+                da = adj.gat_da(g, dy, **kw)
+            ds, dd = adj.gat_datt(x, da, db, **kw)
             ds = ds if ctx.needs_input_grad[2] else None
             dd = dd if ctx.needs_input_grad[3] else None
-        return None, dx, ds, dd, None
+        return None, dx, ds, dd, None, None
 
 
-def spmm_gat(adj, x, att_src, att_dst, slope=0.2):
-    """Attention neighbour aggregation (single-head GAT): `adj` a graph.CSRAdj built for aggr "gat", att_src / att_dst two
-    fp32 vectors of x's width on the device (parameters, or any tensors), slope LeakyReLU's negative slope.  One head only:
-    multi-head attention (heads > 1) is out of scope."""
+def spmm_gat(adj, x, att_src, att_dst, slope=0.2, heads=1):
+    """Attention neighbour aggregation (GAT): `adj` a graph.CSRAdj built for aggr "gat", att_src / att_dst two fp32 vectors of
+    x's width on the device (parameters, or any tensors), slope LeakyReLU's negative slope.  heads = K: K heads partition the
+    channels (head h: columns [h D, (h + 1) D), D = width / K, of x, the result and both vectors), each with its own softmax;
+    K must divide the width and D be a power of two in [4, 256] (ValueError otherwise, before any launch).  heads = 1 is
+    single-head attention at any width."""
     if getattr(adj, "aggr", None) != "gat":
         raise GlassHipError(f"spmm_gat: the adjacency was built for aggr {getattr(adj, 'aggr', None)!r}, not 'gat'")
-    return SpMMGatFn.apply(adj, x, att_src, att_dst, slope)
+    if heads != 1:
+        from .graph import CSRAdj
+        if int(heads) != heads:
+            raise ValueError(f"spmm_gat: heads must be an integer >= 1, not {heads!r}")
+        CSRAdj.gat_head_width(x.shape[-1], int(heads))
+    return SpMMGatFn.apply(adj, x, att_src, att_dst, slope, int(heads))
 
 
 def spmm(adj, x):

@@ -248,6 +248,53 @@ int glass_gat_datt_f32(const float* X, int64_t ldx, const float* da, const float
                        float* datt_src, float* datt_dst,                                 /* [H] each */
                        int64_t n_rows, int64_t H, void* ws, void* stream);
 
+/* K1a, multi-head (csrc/spmm_gat_mh.hip): K heads partition the H channels, head h owns columns [h D, (h + 1) D), D = H / K.
+ *     The operator is block-diagonal: head h's columns of every result are what the single-head entries above give on
+ *     X[:, h D : (h + 1) D] with the matching slices of att_src / att_dst ([H] each, as above).  a, b, L, da, db are [n_rows, K]
+ *     row-major, g is [nnz, K] in forward entry order.  Each entry is its single-head namesake with `int64_t K` after `H`, per
+ *     head: scores, softmax pair, L, D_ih / q_eh (sums over the head's columns), g, da, db; dX[j,c] adds da[j,h(c)] att_src[c] +
+ *     db[j,h(c)] att_dst[c]; datt_*[c] read da / db of c's head.  Workspaces: glass_spmm_gat_mh_ws_bytes = partial slots times
+ *     (H + 2 K) floats, _edge_ and _da_ = slots times K floats, _bwd_ = slots times (H + K) floats, glass_gat_datt_mh_ws_bytes
+ *     as the single-head query.
+ *   Shapes: K >= 1 divides H and D is a power of two with 4 <= D <= 256 (16-byte form under the single-head conditions, scalar
+ *     form otherwise, where a head of 128 or 256 columns spans column passes); K == 1 is served by the single-head entries at
+ *     every H they take.  Anything else -> GLASS_E_UNSUPPORTED, glass_last_error_string naming H, K and D.  K <= 0, and
+ *     whatever the single-head entries refuse, -> the same codes.  No float atomics, bitwise repeatable for a given plan;
+ *     temporaries and vectors are read when the kernels run; slope and K are passed by value. */
+int glass_gat_scores_mh_f32(const float* X, int64_t ldx, const float* att_src, const float* att_dst,
+                            float* a, float* b,                                          /* [n_rows, K] each */
+                            int64_t n_rows, int64_t H, int64_t K, void* stream);
+int64_t glass_spmm_gat_mh_ws_bytes(const int32_t* plan_header_host, int64_t H, int64_t K);
+int glass_spmm_gat_mh_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val,
+                              const float* X, int64_t ldx, const float* a, const float* b, float slope,
+                              float* Y, int64_t ldy, float* L,                           /* [n_rows, H], [n_rows, K] */
+                              int64_t n_rows, int64_t H, int64_t K,
+                              const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_spmm_gat_mh_edge_ws_bytes(const int32_t* plan_header_host, int64_t H, int64_t K);
+int glass_spmm_gat_mh_edge_f32(const int32_t* rowptr, const int32_t* col, const float* val,
+                               const float* X, int64_t ldx, const float* a, const float* b, float slope,
+                               const float* dY, int64_t lddy, const float* Y, int64_t ldy, const float* L,
+                               float* g, float* db,                                      /* [nnz, K], [n_rows, K] */
+                               int64_t n_rows, int64_t H, int64_t K,
+                               const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_spmm_gat_mh_bwd_ws_bytes(const int32_t* plan_t_header_host, int64_t H, int64_t K);
+int glass_spmm_gat_mh_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* val_t, const int32_t* eid_t,
+                              const float* a, const float* b, float slope,
+                              const float* dY, int64_t lddy, const float* L, const float* g, const float* db,
+                              const float* att_src, const float* att_dst,
+                              float* dX, int64_t lddx, float* da,                        /* [n_rows, H], [n_rows, K] */
+                              int64_t n_rows, int64_t H, int64_t K,
+                              const int32_t* plan_t_header_host, const int32_t* plan_t_dev, void* ws, void* stream);
+int64_t glass_spmm_gat_mh_da_ws_bytes(const int32_t* plan_t_header_host, int64_t H, int64_t K);
+int glass_spmm_gat_mh_da_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* val_t, const int32_t* eid_t,
+                             const float* g, float* da,                                  /* [nnz, K], [n_rows, K] */
+                             int64_t n_rows, int64_t H, int64_t K, int vec_form,
+                             const int32_t* plan_t_header_host, const int32_t* plan_t_dev, void* ws, void* stream);
+int64_t glass_gat_datt_mh_ws_bytes(int64_t n_rows, int64_t H);
+int glass_gat_datt_mh_f32(const float* X, int64_t ldx, const float* da, const float* db,
+                          float* datt_src, float* datt_dst,                              /* [H] each */
+                          int64_t n_rows, int64_t H, int64_t K, void* ws, void* stream);
+
 /* K2  normalised edge values of buildAdj (impl/models.py:83-111) on an (row,col)-sorted COO:
  *     deg = segment-sum of w per row, deg<0.5 -> +1; aggr 0=mean w/deg[row], 1=sum w,
  *     2=gcn deg[row]^-1/2 * w * deg[col]^-1/2.  Duplicate (row,col) entries stay separate CSR
