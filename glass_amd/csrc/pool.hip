@@ -73,7 +73,8 @@ __global__ __launch_bounds__(kBlock) void pool_fwd_kernel(const float* __restric
 #pragma unroll
         for (int k = 0; k < VW; ++k) {
             if (mode == GLASS_POOL_MAX) {
-                if (v.a[k] > acc[k]) {  // strict: first occurrence wins a tie
+                // strict: first occurrence wins a tie; a NaN takes the column (the first one) and keeps it
+                if (v.a[k] > acc[k] || (v.a[k] != v.a[k] && acc[k] == acc[k])) {
                     acc[k] = v.a[k];
                     best[k] = j;
                 }
@@ -95,7 +96,8 @@ __global__ __launch_bounds__(kBlock) void pool_fwd_kernel(const float* __restric
             const float ov = lds_v[(r * TC + tc) * VW + k];
             const int oj = lds_j[(r * TC + tc) * VW + k];
             if (mode == GLASS_POOL_MAX) {
-                if (ov > acc[k] || (ov == acc[k] && oj < best[k])) {
+                const bool on = ov != ov, an = acc[k] != acc[k];
+                if (on ? (!an || oj < best[k]) : (!an && (ov > acc[k] || (ov == acc[k] && oj < best[k])))) {
                     acc[k] = ov;
                     best[k] = oj;
                 }
@@ -430,10 +432,8 @@ __global__ __launch_bounds__(kBlock) void pair_gather_kernel(const float* __rest
 #pragma unroll
                 for (int k = 0; k < VW; ++k) {
                     ExactSum tsum{0, 0};
-                    for (int r = 0; r < n_slot; ++r) {
-                        tsum.hi += red[(((r << g_log2) + li) * VW + k) * 2];
-                        tsum.lo += red[(((r << g_log2) + li) * VW + k) * 2 + 1];
-                    }
+                    for (int r = 0; r < n_slot; ++r)
+                        tsum.merge(red[(((r << g_log2) + li) * VW + k) * 2], red[(((r << g_log2) + li) * VW + k) * 2 + 1]);
                     o.a[k] = tsum.value();
                 }
                 o.store(demb + node * lde + c0);
