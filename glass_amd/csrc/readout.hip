@@ -166,38 +166,47 @@ __global__ __launch_bounds__(kBlock) void readout_subgraph_kernel(R1Args a) {
     const int tc = tid & (TC - 1), tr = tid >> a.tc_log2;
     const int c0 = tc * VW;
     const bool ok = c0 < C;
+    // a thread's four accumulator slots: VW == 4 four adjacent columns; VW == 1 the columns c0 + kBlock * k (C <= 4 * kBlock:
+    // beyond kBlock columns TC = kBlock and there is one row slot; up to kBlock only slot 0 is live)
+    constexpr int CS = VW == 4 ? 1 : kBlock;
+    auto okk = [&](int k) { return VW == 4 || c0 + CS * k < C; };
     float accy[4] = {0.f, 0.f, 0.f, 0.f}, acch[4] = {0.f, 0.f, 0.f, 0.f};
     [[maybe_unused]] int best[4] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX};  // (MAX) position of accy; acch = xhat there
     if constexpr (MAX)
 #pragma unroll
         for (int k = 0; k < 4; ++k) accy[k] = -FLT_MAX;
     if (ok) {
-        float mu[VW], rstd[VW], scale[VW], shift[VW], al[VW];
+        float mu[4], rstd[4], scale[4], shift[4], al[4];
 #pragma unroll
-        for (int k = 0; k < VW; ++k) {
-            mu[k] = mu_rstd_s[c0 + k];
-            rstd[k] = mu_rstd_s[C + c0 + k];
-            scale[k] = coef_s[c0 + k];
-            shift[k] = coef_s[C + c0 + k];
-            al[k] = a.alpha[c0 + k];
+        for (int k = 0; k < 4; ++k) {
+            const int c = okk(k) ? c0 + CS * k : c0;
+            mu[k] = mu_rstd_s[c];
+            rstd[k] = mu_rstd_s[C + c];
+            scale[k] = coef_s[c];
+            shift[k] = coef_s[C + c];
+            al[k] = a.alpha[c];
         }
         if (a.Smax <= 2 * rpb) {  // at most two entries per row slot: both were requested before the first barrier
             int it = 0;
             for (int j = tr; j < a.Smax; j += rpb, ++it) {
                 const int64_t node = node_pre[it < 1 ? 0 : 1];
                 if (node < 0 || node >= a.n_nodes) continue;
-                float x[VW];
+                float x[4];
                 if (VW == 4) {
                     const float4 v = *reinterpret_cast<const float4*>(a.jk + node * a.ldj + c0);
-                    x[0] = v.x; x[VW > 1 ? 1 : 0] = v.y; x[VW > 2 ? 2 : 0] = v.z; x[VW > 3 ? 3 : 0] = v.w;
+                    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
                 } else {
-                    x[0] = a.jk[node * a.ldj + c0];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) x[k] = okk(k) ? a.jk[node * a.ldj + c0 + CS * k] : 0.f;
                 }
 #pragma unroll
-                for (int k = 0; k < VW; ++k) {
+                for (int k = 0; k < 4; ++k) {
+                    if (!okk(k)) continue;
                     if constexpr (MAX) {
                         const float y = fmaf(x[k], scale[k], shift[k]);
-                        if (y > accy[k]) {  // strict, j ascending within the slot: the first occurrence wins a tie
+                        // strict, j ascending within the slot: the first occurrence wins a tie; a NaN takes the column (the
+                        // first one) and keeps it: pool.hip's rule
+                        if (y > accy[k] || (y != y && accy[k] == accy[k])) {
                             accy[k] = y;
                             acch[k] = (x[k] - al[k] * mu[k]) * rstd[k];
                             best[k] = j;
@@ -221,26 +230,28 @@ __global__ __launch_bounds__(kBlock) void readout_subgraph_kernel(R1Args a) {
                     const int j = j0 + u * rpb;
                     nd[u] = j >= a.Smax ? -1 : a.stash ? (int64_t)ids[j] : (j0 == tr && u < 2) ? node_pre[u] : prow[j];
                 }
-                float x[U][VW];
+                float x[U][4];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     live[u] = nd[u] >= 0 && nd[u] < a.n_nodes;
                     const float* src = a.jk + (live[u] ? nd[u] : 0) * a.ldj + c0;
                     if (VW == 4) {
                         const float4 v = *reinterpret_cast<const float4*>(src);
-                        x[u][0] = v.x; x[u][VW > 1 ? 1 : 0] = v.y; x[u][VW > 2 ? 2 : 0] = v.z; x[u][VW > 3 ? 3 : 0] = v.w;
+                        x[u][0] = v.x; x[u][1] = v.y; x[u][2] = v.z; x[u][3] = v.w;
                     } else {
-                        x[u][0] = src[0];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) x[u][k] = okk(k) ? src[CS * k] : 0.f;
                     }
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     if (!live[u]) continue;
 #pragma unroll
-                    for (int k = 0; k < VW; ++k) {
+                    for (int k = 0; k < 4; ++k) {
+                        if (!okk(k)) continue;
                         if constexpr (MAX) {
                             const float y = fmaf(x[u][k], scale[k], shift[k]);
-                            if (y > accy[k]) {
+                            if (y > accy[k] || (y != y && accy[k] == accy[k])) {
                                 accy[k] = y;
                                 acch[k] = (x[u][k] - al[k] * mu[k]) * rstd[k];
                                 best[k] = j0 + u * rpb;
@@ -264,11 +275,14 @@ __global__ __launch_bounds__(kBlock) void readout_subgraph_kernel(R1Args a) {
     if (tr == 0 && ok) {
         for (int r = 1; r < rpb; ++r)
 #pragma unroll
-            for (int k = 0; k < VW; ++k) {
+            for (int k = 0; k < 4; ++k) {
+                if (!okk(k)) continue;
                 if constexpr (MAX) {
                     const float ov = red[(r * TC + tc) * RS + k];
                     const int oj = reinterpret_cast<const int*>(red)[(r * TC + tc) * RS + 8 + k];
-                    if (ov > accy[k] || (ov == accy[k] && oj < best[k])) {  // (value, then lower s): pool.hip's rule
+                    // (value, then lower s; a NaN beats every number, the NaN at the lowest s beats the others): pool.hip's rule
+                    const bool on = ov != ov, an = accy[k] != accy[k];
+                    if (on ? (!an || oj < best[k]) : (!an && (ov > accy[k] || (ov == accy[k] && oj < best[k])))) {
                         accy[k] = ov;
                         acch[k] = red[(r * TC + tc) * RS + 4 + k];
                         best[k] = oj;
@@ -279,19 +293,21 @@ __global__ __launch_bounds__(kBlock) void readout_subgraph_kernel(R1Args a) {
                 }
             }
 #pragma unroll
-        for (int k = 0; k < VW; ++k) {
+        for (int k = 0; k < 4; ++k) {
+            if (!okk(k)) continue;
+            const int c = c0 + CS * k;
             if constexpr (MAX) {
                 const bool any = best[k] != INT32_MAX;  // empty row (or no finite entry): pooled 0, no gradient
                 const float pv = any ? accy[k] : 0.f;
-                pooled_s[c0 + k] = pv;
-                xh_s[c0 + k] = any ? acch[k] : 0.f;
-                arg_s[c0 + k] = any ? best[k] : -1;
-                a.pooled[(int64_t)b * C + c0 + k] = pv;
-                a.ws.arg[(int64_t)b * C + c0 + k] = any ? best[k] : -1;
+                pooled_s[c] = pv;
+                xh_s[c] = any ? acch[k] : 0.f;
+                arg_s[c] = any ? best[k] : -1;
+                a.pooled[(int64_t)b * C + c] = pv;
+                a.ws.arg[(int64_t)b * C + c] = any ? best[k] : -1;
             } else {
-                pooled_s[c0 + k] = accy[k] * sc;
-                xh_s[c0 + k] = acch[k];
-                a.pooled[(int64_t)b * C + c0 + k] = accy[k] * sc;
+                pooled_s[c] = accy[k] * sc;
+                xh_s[c] = acch[k];
+                a.pooled[(int64_t)b * C + c] = accy[k] * sc;
             }
         }
     }
@@ -843,11 +859,9 @@ __global__ __launch_bounds__(kBlock) void readout_gather_add_kernel(const int32_
             float add[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                ExactSum tsum{0, 0};
-                for (int r = 0; r < n_slot; ++r) {
-                    tsum.hi += red[(((r << tc_log2) + li) * 4 + k) * 2];
-                    tsum.lo += red[(((r << tc_log2) + li) * 4 + k) * 2 + 1];
-                }
+                ExactSum tsum{0, 0};  // (merge: a sum that leaves hi's range sets the sticky mark instead of wrapping)
+                for (int r = 0; r < n_slot; ++r)
+                    tsum.merge(red[(((r << tc_log2) + li) * 4 + k) * 2], red[(((r << tc_log2) + li) * 4 + k) * 2 + 1]);
                 add[k] = tsum.value();
             }
             float4* d = reinterpret_cast<float4*>(dx + node * lddx + c0);

@@ -40,7 +40,12 @@ CASES = [
     (1024, 3, 9, 1700, 400, "lab"),
     (64, 3, 128, 128, 300, ""), (64, 2, 128, 128, 300, "lab"), (64, 3, 128, 128, 300, "two"),
     (64, 3, 130, 128, 300, ""), (64, 2, 130, 128, 300, "lab"),
+    # the scalar form beyond 256 columns: a thread's four slots take the columns c0 + 256 k.  (The parent commit pooled only
+    # the first 256 columns there and computed everything else from uninitialised LDS: both cases fail on its library.)  C = 260 is
+    # vector-capable and forced scalar by ldj = 261
+    (258, 3, 40, 3, 300, ""), (260, 3, 40, 3, 300, ""),
 ]
+LDJ = {260: 261}  # row stride of jk where it is not C
 
 
 def _case_inputs(C, K, B, Smax, N, seed):
@@ -72,17 +77,21 @@ def _case_inputs(C, K, B, Smax, N, seed):
     return jk, gamma, beta, alpha, pos, Wh, bh, target, (0 if K == 3 else 1)
 
 
-def _call(C, K, B, Smax, N, form, ins):
-    """One call of glass_readout_max_train_f32 on fresh buffers; returns its outputs on the CPU."""
+def _call(C, K, B, Smax, N, form, ins, stats_jk=None):
+    """One call of glass_readout_max_train_f32 on fresh buffers; returns its outputs on the CPU.  stats_jk: the matrix the
+    caller's GraphNorm statistics are taken from (default: jk itself)."""
     from glass_amd import _lib, stack
     from glass_amd.ops import _stream
     lib = _lib.load()
     jk, gamma, beta, alpha, pos, Wh, bh, target, loss_mode = ins
-    mu, rstd = R.graphnorm_stats(jk.double(), alpha.double(), EPS)
+    mu, rstd = R.graphnorm_stats((jk if stats_jk is None else stats_jk).double(), alpha.double(), EPS)
     scale = (gamma.double() * rstd).float()
     shift = (beta.double() - scale.double() * alpha.double() * mu).float()
     saved = torch.cat([mu.float(), rstd.float(), scale, shift]).to(DEV)
-    d = {k: v.to(DEV).contiguous() for k, v in dict(jk=jk, gamma=gamma, alpha=alpha, pos=pos, Wh=Wh, bh=bh).items()}
+    ldj = LDJ.get(C, C)
+    jk_pad = torch.full((N, ldj), float("nan"))
+    jk_pad[:, :C] = jk
+    d = {k: v.to(DEV).contiguous() for k, v in dict(jk=jk_pad, gamma=gamma, alpha=alpha, pos=pos, Wh=Wh, bh=bh).items()}
     tgt = target.to(DEV).contiguous()
     f32 = dict(dtype=torch.float32, device=DEV)
     out = dict(pooled=torch.full((B, C), 7.0, **f32), logits=torch.full((B, K), 7.0, **f32), loss=torch.full((), 7.0, **f32),
@@ -92,7 +101,7 @@ def _call(C, K, B, Smax, N, form, ins):
     ws = torch.zeros(ws_bytes // 8 + 1, dtype=torch.float64, device=DEV)
     one = torch.ones((), **f32)
     largs, labels = (0, 0, 0), None
-    if form in ("lab", "two") or C % 4:
+    if form in ("lab", "two") or C % 4 or ldj % 4:
         labels = stack.BatchLabels(N, pos.numel(), DEV)
         labels.load(d["pos"])
         largs = (labels.mask.data_ptr(), labels.rows.data_ptr(), labels.count.data_ptr())
@@ -103,7 +112,7 @@ def _call(C, K, B, Smax, N, form, ins):
     assert (sws_bytes > 0) == (B * Smax > 16384)
     sws = torch.empty(sws_bytes + 16, dtype=torch.uint8, device=DEV) if sws_bytes else None
     rc = lib.glass_readout_max_train_f32(
-        d["jk"].data_ptr(), C, saved.data_ptr(), d["gamma"].data_ptr(), d["alpha"].data_ptr(), d["pos"].data_ptr(), B, Smax,
+        d["jk"].data_ptr(), ldj, saved.data_ptr(), d["gamma"].data_ptr(), d["alpha"].data_ptr(), d["pos"].data_ptr(), B, Smax,
         d["Wh"].data_ptr(), d["bh"].data_ptr(), tgt.data_ptr(), loss_mode, K, one.data_ptr(), out["pooled"].data_ptr(),
         out["logits"].data_ptr(), out["loss"].data_ptr(), out["djk"].data_ptr(), C, out["dWh"].data_ptr(), out["dbh"].data_ptr(), 0,
         out["dgamma"].data_ptr(), out["dbeta"].data_ptr(), out["dalpha"].data_ptr(), 0, ws.data_ptr(), N, C, *largs, 0,
@@ -114,6 +123,7 @@ def _call(C, K, B, Smax, N, form, ins):
     arg = ws.view(torch.uint8)[off:off + 4 * B * C].view(torch.int32).reshape(B, C)
     res = {k: v.cpu() for k, v in out.items()}
     res["arg"] = arg.cpu().to(torch.int64)
+    res["saved"] = saved.cpu()
     return res
 
 
@@ -132,6 +142,7 @@ def test_max_readout_entry_vs_fp64_restatement(C, K, B, Smax, N, form):
     again = _call(C, K, B, Smax, N, form, ins)
     for k in got:
         assert torch.equal(got[k], again[k]), f"{k}: two calls on the same inputs differ"
+    got.pop("saved")
     assert torch.equal(got["arg"], want["arg"])
     errs = {k: rel_inf(got[k], want[k]) for k in ("pooled", "logits", "loss", "djk")}
     keys = ("dWh", "dbh", "dgamma", "dbeta", "dalpha")
@@ -146,6 +157,47 @@ def test_max_readout_entry_vs_fp64_restatement(C, K, B, Smax, N, form):
     assert int(got["arg"][8, 0]) == 0
     assert got["djk"][21, 0].item() == got["djk"][22, 0].item()
     assert got["djk"][20, 0].item() != got["djk"][22, 0].item()
+
+
+def test_max_readout_nan_takes_the_column_like_the_pooling_kernel():
+    """NaNs in one column of jk at the nodes of two positions of one row that fall into different row slots (C = 64: 16
+    slots; positions 5 and 18 are slots 5 and 2, so the slot fold meets the LATER NaN first), and at a third position in the
+    first one's slot; statistics from the clean matrix.  pool.hip's rule: a NaN takes the column, the first NaN by position is
+    the argmax and carries the gradient.  The argmax positions equal what glass_segment_pool_f32's max mode returns for the
+    same y, in every row and column.  (The parent commit's compare `y > acc` dropped every NaN: the column pooled to its
+    largest number; this test fails on its library.)"""
+    from glass_amd import _lib
+    from glass_amd.ops import _stream
+    lib = _lib.load()
+    C, K, B, Smax, N = 64, 3, 24, 40, 300
+    ins = _case_inputs(C, K, B, Smax, N, seed=77)
+    jk, gamma, beta, alpha, pos, Wh, bh, target, loss_mode = ins
+    row, col = 10, 3
+    pos[row, 5], pos[row, 18], pos[row, 21] = 250, 251, 252
+    dirty = jk.clone()
+    dirty[250, col] = dirty[251, col] = dirty[252, col] = float("nan")
+    clean = _call(C, K, B, Smax, N, "", ins)
+    got = _call(C, K, B, Smax, N, "", (dirty, ) + ins[1:], stats_jk=jk)
+    assert int(got["arg"][row, col]) == 5 and bool(torch.isnan(got["pooled"][row, col]))
+    # the pooling kernel on the same y (fp32 affine of the same saved scale | shift; the columns are separated, so one rounding
+    # of y moves no argmax between numbers)
+    scale, shift = got["saved"][2 * C:3 * C], got["saved"][3 * C:]
+    y = (dirty * scale + shift).to(DEV).contiguous()
+    posd = pos.to(DEV).contiguous()
+    out = torch.empty(B, C, dtype=torch.float32, device=DEV)
+    node = torch.full((B, C), -7, dtype=torch.int32, device=DEV)
+    rc = lib.glass_segment_pool_f32(y.data_ptr(), C, posd.data_ptr(), B, Smax, _lib.POOL_MODES["max"], out.data_ptr(), C, node.data_ptr(),
+                                    N, C, _stream())
+    assert rc == 0, lib.glass_last_error_string()
+    torch.cuda.synchronize()
+    node = node.cpu().to(torch.int64)
+    mine = torch.where(got["arg"] >= 0, pos.gather(1, got["arg"].clamp(min=0)), torch.full_like(got["arg"], -1))
+    assert torch.equal(mine, node)
+    # rows that name none of the three nodes keep their argmax; the NaN reaches d jk of node 250 in that column (the gradient's row)
+    touched = ((pos == 250) | (pos == 251) | (pos == 252)).any(1)
+    assert torch.equal(got["arg"][~touched], clean["arg"][~touched])
+    hit = got["arg"][:, col] != clean["arg"][:, col]
+    assert bool(hit[row]) and bool((got["arg"][:, :col] == clean["arg"][:, :col]).all()) and bool((got["arg"][:, col + 1:] == clean["arg"][:, col + 1:]).all())
 
 
 # ---- model level -------------------------------------------------------------------------------------------------------
