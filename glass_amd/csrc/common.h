@@ -67,9 +67,10 @@ __device__ __forceinline__ float act_fast(int act, float h) {
     const float e = act == GLASS_ACT_ELU ? 1.f : 0.f;
     return h > 0.f ? h : fmaf(e, __expf(h), -e);
 }
+// (ReLU of NaN is NaN, as torch.relu's and act_fast's: `h > 0` alone is false for NaN and wrote a clean 0 over a diverged column)
 __device__ __forceinline__ float act_exact(int act, float h) {
     if (act == GLASS_ACT_NONE) return h;
-    return h > 0.f ? h : (act == GLASS_ACT_ELU ? expm1f(h) : 0.f);
+    return h > 0.f ? h : (act == GLASS_ACT_ELU ? expm1f(h) : (h != h ? h : 0.f));
 }
 __device__ __forceinline__ float act_grad(int act, float h) {
     if (act == GLASS_ACT_NONE) return 1.f;

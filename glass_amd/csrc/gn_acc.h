@@ -7,12 +7,19 @@
 // addition is associative, so the result does not depend on the order the workgroups arrive in: bitwise repeatable, which
 // float atomics are not — and every consumer workgroup folds the replicas itself in its prologue (one round trip of 16-32
 // loads per thread).  Representation of a partial sum v (a double): v * 2^52 = hi * 2^40 + lo, hi = floor(v * 2^12) as int64,
-// lo in [0, 2^40): absolute resolution 2^-52 (2.2e-16) per workgroup partial, range |sum| < 2^50 — far inside what fp32
-// activations and their squares can reach over 10^6 rows.  A partial that is NaN, infinite or out of that range does not
-// saturate into a finite wrong sum: it sets a STICKY POISON BIT — bit 63 of the lo limb, by an integer atomicOr; the lo limbs
-// of up to 2^22 in-range adds stay below 2^62, so no carry ever reaches or clears it, and OR commutes with itself like the
-// adds do — and every fold turns a poisoned column into NaN, which the consumers' arithmetic then propagates exactly as the
-// reference's float sums do (a diverging run stays visible; tests/test_gpu_model.py::test_nonfinite_values_reach_the_outputs).
+// lo in [0, 2^40): absolute resolution 2^-52 (2.2e-16) per workgroup partial, documented range |sum| < 2^50 — far inside what
+// fp32 activations and their squares can reach over 10^6 rows.  A single PARTIAL that is NaN, infinite or beyond 4.0e18 / scale
+// (|v| > 9.8e14 forward, 2.4e11 backward) does not saturate into a finite wrong sum: it sets a STICKY POISON BIT — bit 63 of the
+// lo limb, by an integer atomicOr; the lo limbs of up to 2^22 in-range adds stay below 2^62, so no carry ever reaches or clears
+// it, and OR commutes with itself like the adds do — and every fold turns a poisoned column into NaN, which the consumers'
+// arithmetic then propagates exactly as the reference's float sums do (a diverging run stays visible;
+// tests/test_gpu_model.py::test_nonfinite_values_reach_the_outputs, tests/test_gpu_graphnorm.py).
+// WHAT THE LIMBS GUARANTEE, exactly: the folded sum is the integer sum of the encoded partials while the sum over a replica's
+// adds of |hi| — and over the folded replicas — stays below 2^63.  The SUM is not range-checked: a total beyond that wraps
+// modulo 2^64 into a FINITE value and is NOT poisoned (only a single partial out of range is).  The documented range
+// |sum| < 2^50 (forward) / 2^38 (backward) lies inside the guarantee for that reason only — 2^50 * 2^12 = 2^38 * 2^24 = 2^62 —
+// and nothing here detects a run that leaves it through many in-range partials.  (Restated in integers and checked by
+// tests/graphnorm_oracle.py, tests/test_graphnorm_host.py.)
 // Resolution caveat: contributions below 2^-52 (forward) / 2^-64 (backward) of a PARTIAL are truncated — "exact" means the
 // integer sum of the partials is exact and order-independent, not that each partial is represented exactly.  Layout: int64
 // [kAccRep][2 quantities][C][2 limbs], zeroed once per step by the prologue launch (glass_step_prologue_f32).

@@ -384,6 +384,7 @@ extern "C" int glass_graphnorm_bwd_f32(const float* dy, int64_t lddy, const floa
     GLASS_REQUIRE(n_rows > 0 && C > 0 && lddy >= C && ldx >= C && lddx >= C && (!addend || ldadd >= C),
                   "graphnorm_bwd: bad sizes");
     GLASS_REQUIRE(p_drop >= 0.f && p_drop < 1.f && (p_drop == 0.f || rng_state), "graphnorm_bwd: bad dropout args");
+    GLASS_REQUIRE(act_code_ok(act), "graphnorm_bwd: bad act %d", act);
     hipStream_t st = (hipStream_t)stream;
     const bool vec = C % 4 == 0 && lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && aligned16(dy) && aligned16(x) &&
                      aligned16(dx) && (!addend || (ldadd % 4 == 0 && aligned16(addend)));
@@ -422,6 +423,7 @@ extern "C" int glass_graphnorm_bwd_from_stats_f32(const float* dy, int64_t lddy,
     GLASS_REQUIRE(n_rows > 0 && C > 0 && nblk != 0 && nblk < (1ll << 31) && lddy >= C && ldx >= C && lddx >= C &&
                       (!addend || ldadd >= C),
                   "graphnorm_bwd_from_stats: bad sizes");
+    GLASS_REQUIRE(act_code_ok(act), "graphnorm_bwd_from_stats: bad act %d", act);
     if (nblk < 0) {
         // `partial` = the exact accumulators of gn_acc.h (what the data-gradient epilogues added to with gn_exact): finalize
         // and apply as ONE launch
