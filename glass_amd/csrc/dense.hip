@@ -3377,6 +3377,7 @@ static int dgrad_launch(const float* dsrc, int64_t ldd, const float* T, int64_t 
                         double* gn_partial, const float* gn_x, int64_t gn_ldx, const float* gn_saved,
                         const float* gn_alpha, int gn_act, float gn_p_drop, uint64_t gn_call_id, int gn_exact,
                         const BwdWgrad* wg, void* stream) {
+    GLASS_REQUIRE(act_code_ok(act), "dual_linear_dgrad: bad act %d", act);  // (an unknown code ran as ReLU's formula: act_grad)
     GLASS_REQUIRE(dsrc && mask && WT && out && n_nodes > 0, "dual_linear_dgrad: null pointer");
     GLASS_REQUIRE(p_drop >= 0.f && p_drop < 1.f && (p_drop == 0.f || (rng_state && n_out == H)),
                   "dual_linear_dgrad: bad dropout args (the masked output must be the [N,H] layer input)");
