@@ -63,7 +63,15 @@ def parse_args(argv=None):
     p.add_argument("--gat_heads", type=int, default=1,
                    help="(extension) attention heads of --aggr gat: they partition the hidden channels, so the count must divide "
                         "hidden_dim and leave a power of two in [4, 256] channels per head (default: 1)")
+    p.add_argument("--edge_saliency", type=str, default=None, metavar="PATH",
+                   help="(extension) after the last repeat write PATH (.npy, one fp32 per edge of the graph): the mean over the "
+                        "test split's batches of |d loss / d edge_weight| of the trained model; aggregations mean, sum and gcn "
+                        "only, not with --use_zeroone")
     args = p.parse_args(argv)
+    if args.edge_saliency is not None and args.use_zeroone:
+        p.error("--edge_saliency is not available with --use_zeroone (no edge-weight gradient on the replicated path)")
+    if args.edge_saliency is not None and args.aggr not in (None, "mean", "sum", "gcn"):
+        p.error(f"--edge_saliency needs --aggr mean, sum or gcn (no edge-weight gradient for {args.aggr})")
     if args.gat_heads < 1:
         p.error("--gat_heads must be an integer >= 1")
     if args.use_zeroone and args.use_maxzeroone:
@@ -227,7 +235,23 @@ class Run:
             print(f"end: epoch {epochs}, train time {seconds:.2f} s, val {val:.3f}, tst {tst:.3f}", flush=True)
             results.append(tst)
         print(f"average {np.average(results):.3f} error {np.std(results) / np.sqrt(len(results)):.3f}")
+        if getattr(self.args, "edge_saliency", None) is not None and self.args.repeat > 0:
+            self.write_edge_saliency(model, self.loaders(batch_size)[2], self.args.edge_saliency)
         return results
+
+    def write_edge_saliency(self, model, tst_loader, path):
+        """--edge_saliency: the mean over the test split's batches of |d loss / d edge_weight| of `model`, [E] fp32 as .npy."""
+        from glass_amd import explain
+        total, n_batches = None, 0
+        for batch in tst_loader:
+            x, ei, ea, pos = batch[:4]
+            z = batch[4] if len(batch) > 5 else None
+            g = explain.edge_saliency(model, x, ei, ea, pos, z, loss_fn=self.loss_fn, y=batch[-1]).abs()
+            total = g if total is None else total + g
+            n_batches += 1
+        with open(path, "wb") as f:
+            np.save(f, (total / n_batches).cpu().numpy().astype(np.float32))
+        print(f"edge saliency of {n_batches} test batches -> {path}", flush=True)
 
 
 class Patience:
@@ -274,6 +298,9 @@ def main(argv=None):
         params["aggr"] = args.aggr
     if args.gat_heads != 1:  # (the flag, where given, instead of the config file's `gat_heads`)
         params["gat_heads"] = args.gat_heads
+    if args.edge_saliency is not None and params.get("aggr", "mean") not in ("mean", "sum", "gcn"):
+        raise SystemExit(f"--edge_saliency needs aggr mean, sum or gcn; the configuration says {params['aggr']!r} "
+                         "(no edge-weight gradient for the other aggregations)")
     run.split()
     return run.test(**params)
 

@@ -109,6 +109,11 @@ SIGNATURES = {
     "glass_gat_datt_mh_ws_bytes": (c_int64, [_I, _I]),
     "glass_gat_datt_mh_f32": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "glass_adj_values_f32": (c_int, [_P, _P, _P, _I, c_int, _P, _P, _P]),
+    "glass_spmm_dval_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_dval_f32": (c_int, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "glass_adj_colsum_ws_bytes": (c_int64, [_P]),
+    "glass_adj_colsum_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "glass_adj_values_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, c_int, _P, _P]),
     "glass_maxzoz_i64": (c_int, [_P, _I, _P, _I, _P]),
     "glass_embed_label_f32": (c_int, [_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _P]),
     "glass_mix_fwd_f32": (c_int, [_P, _I, _P, c_double, c_int, _P, _I, _I, _I, _P]),

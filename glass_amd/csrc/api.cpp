@@ -216,3 +216,26 @@ extern "C" int glass_seg_collate_centre(const int32_t* sub_ptr, const int32_t* s
                                             val_out, centre_ptr, centre_local, ids, n_batch, node_off, brow_in, brow_out,
                                             bcol_in, bval_in, bcol_out, bval_out, node_map, pos, pos_width, mark, stream);
 }
+
+// ---- K1w  backward of K2 (glass_adj_values_f32): host-side validation, then the launch in spmm_edge.hip ----------------------
+namespace glass {
+int adj_values_bwd_launch(const int32_t*, const int32_t*, const int32_t*, const float*, const float*, const float*, const float*,
+                          int64_t, int64_t, int, float*, void*);
+}  // namespace glass
+
+extern "C" int glass_adj_values_bwd_f32(const int32_t* rowptr, const int32_t* col, const int32_t* perm, const float* deg,
+                                        const float* dval, const float* R, const float* C, int64_t n_rows, int64_t nnz,
+                                        int aggr, float* dw, void* stream) {
+    if (aggr < 0 || aggr > 2) {
+        glass::set_error("adj_values_bwd: unknown aggr %d (0=mean,1=sum,2=gcn)", aggr);
+        return GLASS_E_UNSUPPORTED;
+    }
+    SEG_REQUIRE(n_rows >= 0 && n_rows < INT32_MAX && nnz >= 0 && nnz < INT32_MAX, "adj_values_bwd: negative or too large size");
+    if (n_rows == 0) return 0;
+    SEG_REQUIRE(rowptr, "adj_values_bwd: null rowptr");
+    SEG_REQUIRE(nnz == 0 || (perm && dval && dw), "adj_values_bwd: null perm/dval/dw");
+    SEG_REQUIRE(aggr == 1 || nnz == 0 || (deg && R), "adj_values_bwd: aggr mean and gcn need deg and R");
+    SEG_REQUIRE(aggr != 2 || nnz == 0 || (col && C), "adj_values_bwd: aggr gcn needs col and C");
+    if (nnz == 0) return 0;
+    return glass::adj_values_bwd_launch(rowptr, col, perm, deg, dval, R, C, n_rows, nnz, aggr, dw, stream);
+}

@@ -5,10 +5,12 @@ import functools
 import torch.nn as nn
 
 
-def build_glass(hidden, layers, max_deg, out_ch, aggr, pool, z_ratio, dropout=0.0, jk=True, pad_width=True, gat_heads=1):
+def build_glass(hidden, layers, max_deg, out_ch, aggr, pool, z_ratio, dropout=0.0, jk=True, pad_width=True, gat_heads=1,
+                live_edge_weight=False):
     """pad_width: a hidden width no kernel family serves (33..63, 65..127, ...) is built at the next family width with
     zero padding — exact, same logical parameters, logical state_dict (glass_amd/widths.py); False keeps the width as it
-    is (the per-op path with library GEMMs serves it).  gat_heads: the attention heads of aggr "gat" (GLASSConv)."""
+    is (the per-op path with library GEMMs serves it).  gat_heads: the attention heads of aggr "gat" (GLASSConv).
+    live_edge_weight: the layers aggregate with each call's edge weights, differentiably (GLASSConv)."""
     from impl import models
     pools = {"mean": models.MeanPool, "max": models.MaxPool, "sum": models.AddPool, "size": models.SizePool}
     if pool not in pools:
@@ -20,7 +22,7 @@ def build_glass(hidden, layers, max_deg, out_ch, aggr, pool, z_ratio, dropout=0.
                                                        gat_heads=gat_heads),
                                 gn=True)
         mlp = nn.Linear(h * layers if jk else h, out_ch)
-        return models.GLASS(conv, nn.ModuleList([mlp]), nn.ModuleList([pools[pool]()]))
+        return models.GLASS(conv, nn.ModuleList([mlp]), nn.ModuleList([pools[pool]()]), live_edge_weight=live_edge_weight)
 
     if not pad_width:
         return build(hidden)

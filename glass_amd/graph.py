@@ -10,6 +10,9 @@ HBM layout (all on the device the graph lives on):
   rowptr_t, col_t, val_t                                      CSR of A^T (for the backward)
   plan / plan_t int32[...]                                    opaque K1 schedules
   eid_t int32[nnz]                                            aggr "max" and "gat": forward index of each entry of A^T
+  perm int64[nnz]                                             the build permutation: entry e is the caller's edge perm[e]
+aggr "sum", "mean" and "gcn" can also be evaluated at OTHER edge weights on the same structure, with the gradient with respect
+to them (values_of / dval / colsum / values_bwd: K1w, ops.spmm_w); what that needs beyond perm is built on first use.
 aggr "max", "softmax" and "gat" keep the raw edge weights in val (the values of "sum"); "softmax" and "gat" require them > 0.
 Duplicate (row,col) entries are kept as separate entries: they add up in the product exactly as in
 the reference's uncoalesced COO matmul.
@@ -64,14 +67,18 @@ class CSROperand:
             self._ws[key] = ws
         return ws
 
-    def spmm(self, x, out=None):
+    def spmm(self, x, out=None, val=None):
+        """val: other values for the same entries (fp32 [nnz] on the device: CSRAdj.values_of) instead of the stored ones."""
         assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32 and x.is_cuda
         assert x.shape[0] == self.n_cols, f"X has {x.shape[0]} rows, matrix has {self.n_cols} columns"
         H = x.shape[1]
         if out is None:
             out = torch.empty((self.n_rows, H), dtype=torch.float32, device=x.device)
         assert out.stride(1) == 1 and out.shape == (self.n_rows, H)
-        rc = _lib.load().glass_spmm_csr_f32(self.rowptr.data_ptr(), self.col.data_ptr(), self.val.data_ptr(),
+        if val is None:
+            val = self.val
+        assert val.dtype == torch.float32 and val.shape == self.val.shape and val.is_contiguous() and val.device == self.val.device
+        rc = _lib.load().glass_spmm_csr_f32(self.rowptr.data_ptr(), self.col.data_ptr(), val.data_ptr(),
                                             x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), self.n_rows, H,
                                             self.header.ctypes.data, self.plan.data_ptr(),
                                             self.workspace(H).data_ptr(), torch.cuda.current_stream().cuda_stream)
@@ -168,6 +175,7 @@ class CSRAdj:
         col_t = row[perm_t].to(torch.int32).contiguous()
         val_t = val[perm_t].contiguous()
         self.n_node, self.aggr = n, aggr
+        self.perm = perm  # entry e of the forward CSR is edge perm[e] of the caller's edge_index (int64, as argsort left it)
         self.fwd = CSROperand(rowptr, col32, val, n, n)
         self.bwd = CSROperand(rowptr_t, col_t, val_t, n, n)
         if aggr in ("max", "gat"):
@@ -192,6 +200,103 @@ class CSRAdj:
                 self._retired_ws.append(ws)  # (a captured graph may still launch with this pointer: never handed back)
             ws = self._aggr_ws[key] = torch.empty(max((nbytes + 7) // 8, 2), dtype=torch.float64, device=self.fwd.rowptr.device)
         return ws
+
+    # ---- K1w: the gradient with respect to the edge weights (aggr "sum", "mean", "gcn"; csrc/spmm_edge.hip) -----------------
+    def _edge_grad_state(self, what):
+        """(eid_t, perm32, workspaces), built the first time the edge-weight path asks: eid_t is the stable sort that built the
+        transpose, made again from the stored CSR (the same permutation), perm32 the build permutation as the kernel reads it."""
+        if self.aggr not in _lib.AGGR_MODES:
+            raise _lib.GlassHipError(f"CSRAdj.{what}: no edge-weight gradient for aggr {self.aggr!r} (only 'sum', 'mean', 'gcn')")
+        st = self.__dict__.get("_edge_grad")
+        if st is None:
+            rp = self.fwd.rowptr.to(torch.int64)
+            row = torch.repeat_interleave(torch.arange(self.n_node, device=rp.device), rp[1:] - rp[:-1])
+            eid_t = torch.argsort(self.fwd.col.to(torch.int64) * self.n_node + row, stable=True).to(torch.int32).contiguous()
+            st = self._edge_grad = (eid_t, self.perm.to(torch.int32).contiguous(), {})
+        return st
+
+    def _edge_ws(self, key, nbytes):
+        if nbytes < 0:
+            raise _lib.GlassHipError("bad plan header")
+        pool = self._edge_grad_state("workspace")[2]
+        key = (key, _ws_branch)
+        ws = pool.get(key)
+        if ws is None:
+            ws = pool[key] = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=self.fwd.rowptr.device)
+        return ws
+
+    def values_of(self, w):
+        """(val, val_t, deg) for the caller-order weight vector w (fp32 [E] on the device, the order of the edge_index this
+        adjacency was built from): what the constructor would store for it — K2 on the permuted weights, the transpose a permute
+        of the result.  The stored values are not touched."""
+        op = self.fwd
+        if self.aggr in _lib.AGGR_MODES and (w.dim() != 1 or w.shape[0] != op.nnz or w.dtype != torch.float32 or
+                                             w.device != op.rowptr.device):  # (before any launch)
+            raise ValueError(f"edge weights: expected {op.nnz} fp32 on {op.rowptr.device}, got {tuple(w.shape)} {w.dtype} on {w.device}")
+        eid_t, _p, _ws = self._edge_grad_state("values_of")
+        ws = w.detach()[self.perm].contiguous()
+        deg = torch.empty(self.n_node, dtype=torch.float32, device=w.device)
+        val = torch.empty(op.nnz, dtype=torch.float32, device=w.device)
+        rc = _lib.load().glass_adj_values_f32(op.rowptr.data_ptr(), op.col.data_ptr(), ws.data_ptr(), self.n_node,
+                                              _lib.AGGR_MODES[self.aggr], deg.data_ptr(), val.data_ptr(),
+                                              torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_adj_values_f32")
+        return val, val[eid_t.to(torch.int64)].contiguous(), deg
+
+    def dval(self, dy, x, val):
+        """(dval, R) = the sampled dense-dense product over the forward CSR: dval [nnz] the dot of dy[destination] and
+        x[source] of every entry, in forward entry order; R [N] the row sums of dval * val."""
+        self._edge_grad_state("dval")
+        op = self.fwd
+        ldx = self._softmax_operand(x, op.n_cols, "X")
+        lddy = self._softmax_operand(dy, op.n_rows, "dY")
+        assert dy.shape == x.shape
+        assert val.dtype == torch.float32 and val.shape == (op.nnz, ) and val.is_contiguous() and val.is_cuda
+        H = x.shape[1]
+        lib = _lib.load()
+        dv = torch.empty(max(op.nnz, 1), dtype=torch.float32, device=x.device)[:op.nnz]
+        R = torch.empty(op.n_rows, dtype=torch.float32, device=x.device)
+        ws = self._edge_ws("dval", lib.glass_spmm_dval_ws_bytes(op.header.ctypes.data, H))
+        rc = lib.glass_spmm_dval_f32(op.rowptr.data_ptr(), op.col.data_ptr(), val.data_ptr(), x.data_ptr(), ldx, dy.data_ptr(),
+                                     lddy, dv.data_ptr(), R.data_ptr(), op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
+                                     ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_dval_f32")
+        return dv, R
+
+    def colsum(self, dval, val_t):
+        """C [N] = the column sums of dval * val, over the transposed CSR (aggr "gcn" needs them)."""
+        eid_t, _p, _ws = self._edge_grad_state("colsum")
+        op = self.bwd
+        for a in (dval, val_t):
+            assert a.dtype == torch.float32 and a.shape == (op.nnz, ) and a.is_contiguous() and a.is_cuda
+        lib = _lib.load()
+        C = torch.empty(op.n_rows, dtype=torch.float32, device=dval.device)
+        ws = self._edge_ws("colsum", lib.glass_adj_colsum_ws_bytes(op.header.ctypes.data))
+        rc = lib.glass_adj_colsum_f32(op.rowptr.data_ptr(), op.col.data_ptr(), val_t.data_ptr(), eid_t.data_ptr(), dval.data_ptr(),
+                                      C.data_ptr(), op.n_rows, op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
+                                      torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_adj_colsum_f32")
+        return C
+
+    def values_bwd(self, dval, R, C, w, deg=None):
+        """dw [E], in the caller's edge order: the backward of values_of at w for the entry gradients dval (with their row sums R
+        and, for "gcn", column sums C; None where the aggregation does not read them).  deg: values_of(w)'s third result when
+        the caller kept it; made again from w otherwise."""
+        _e, perm32, _ws = self._edge_grad_state("values_bwd")
+        op = self.fwd
+        if deg is None and self.aggr != "sum":
+            deg = self.values_of(w)[2]
+        assert dval.dtype == torch.float32 and dval.shape == (op.nnz, ) and dval.is_contiguous() and dval.is_cuda
+        for a in (R, C, deg):
+            assert a is None or (a.dtype == torch.float32 and a.shape == (self.n_node, ) and a.is_contiguous() and a.is_cuda)
+        dw = torch.empty(op.nnz, dtype=torch.float32, device=dval.device)
+        ptr = lambda a: None if a is None else a.data_ptr()
+        rc = _lib.load().glass_adj_values_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), perm32.data_ptr(), ptr(deg),
+                                                  dval.data_ptr(), ptr(R), ptr(C), self.n_node, op.nnz,
+                                                  _lib.AGGR_MODES[self.aggr], dw.data_ptr(),
+                                                  torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_adj_values_bwd_f32")
+        return dw
 
     def _need_max(self, what):
         if self.aggr != "max":

@@ -178,16 +178,34 @@ def _reset_gat_att(conv):
             conv.att_dst.uniform_(-bound, bound)
 
 
+def set_live_edge_weight(emb):
+    """Every GLASSConv layer of `emb` to live edge weights (what their constructor argument sets)."""
+    for c in emb.convs:
+        if getattr(c, "aggr", None) not in ("sum", "mean", "gcn") or not isinstance(c, GLASSConv):
+            raise ValueError(f"live_edge_weight needs GLASSConv layers with aggr 'sum', 'mean' or 'gcn', not "
+                             f"{type(c).__name__} with aggr {getattr(c, 'aggr', None)!r}")
+    for c in emb.convs:
+        c.live_edge_weight = True
+
+
 class GLASSConv(nn.Module):
     """Labeled message-passing layer: two weight sets (index 1 = labeled, 0 = unlabeled) mixed by
     z_ratio before and after the neighbour aggregation.  aggr "gat" (an extension): attention over the mixed messages, the
     layer owns att_src and att_dst ([out_channels] each) and the constants gat_slope (LeakyReLU's negative slope) and
     gat_heads: K heads partition the channels (head h: channels [h D, (h + 1) D), D = out_channels / K, of the messages, the
     result and both vectors), each with its own softmax; the output width and the state_dict do not depend on K.  K must
-    divide out_channels and D be a power of two in [4, 256] (ValueError at construction; other aggregations ignore it)."""
+    divide out_channels and D be a power of two in [4, 256] (ValueError at construction; other aggregations ignore it).
+    live_edge_weight (an extension, aggr "sum" / "mean" / "gcn" only: ValueError otherwise): the layer aggregates with the
+    `edge_weight` of EACH call (ops.spmm_w: the normalisation is evaluated again, and the result is differentiable in the
+    weights) on the structure cached from the first call; no parameter, the same state_dict.  Such a layer runs as per-op
+    autograd nodes: the stack program (stack.StackProgram, the captured step program of step.TrainStep) declines its model."""
     def __init__(self, in_channels: int, out_channels: int, activation=nn.ReLU(inplace=True), aggr="mean",
-                 z_ratio=0.8, dropout=0.2, softmax_t=1.0, gat_slope=0.2, gat_heads=1):
+                 z_ratio=0.8, dropout=0.2, softmax_t=1.0, gat_slope=0.2, gat_heads=1, live_edge_weight=False):
         super().__init__()
+        if live_edge_weight and aggr not in ("sum", "mean", "gcn"):
+            raise ValueError(f"GLASSConv: live_edge_weight needs aggr 'sum', 'mean' or 'gcn', not {aggr!r} (no edge-weight "
+                             "gradient for the other aggregations)")
+        self.live_edge_weight = bool(live_edge_weight)
         self.trans_fns = nn.ModuleList([nn.Linear(in_channels, out_channels), nn.Linear(in_channels, out_channels)])
         self.comb_fns = nn.ModuleList([nn.Linear(in_channels + out_channels, out_channels),
                                        nn.Linear(in_channels + out_channels, out_channels)])
@@ -225,11 +243,16 @@ class GLASSConv(nn.Module):
         `batch`: an ops.Replicas when x_ holds R replicas of the graph's rows (replica-major, [R * N, H]) with one label byte
         per replica row: the aggregation and the GraphNorm then run per replica (ops.spmm_rep, ops.graphnorm_rep); the dense
         calls key only on the row's label byte and take the R * N rows as they are."""
+        if self.live_edge_weight and batch is not None:
+            raise ValueError("GLASSConv: live_edge_weight has no replicated form (exact zero-one labels: `batch` given)")
         if self.adj is None:
-            self.adj = buildAdj(edge_index, edge_weight, x_.shape[0] if batch is None else batch.N, self.aggr)
+            self.adj = buildAdj(edge_index, edge_weight.detach() if self.live_edge_weight else edge_weight,
+                                x_.shape[0] if batch is None else batch.N, self.aggr)
         if batch is not None and x_.shape[0] != batch.R * batch.N:
             raise ValueError(f"GLASSConv: {x_.shape[0]} rows for {batch!r}")
-        if batch is not None:
+        if self.live_edge_weight:
+            agg = lambda m: ops.spmm_w(self.adj, m, edge_weight)
+        elif batch is not None:
             agg = lambda m: ops.spmm_rep(self.adj, m, batch.R)
         elif self.aggr == "softmax":
             agg = lambda m: ops.spmm_softmax(self.adj, m, self.t)
@@ -267,10 +290,13 @@ class GLASSConv(nn.Module):
 
 class EmbZGConv(nn.Module):
     """Embedding of the integer node feature + label mask, then `num_layers` GLASSConv layers
-    with GraphNorm / activation / dropout between them and optional JK concatenation."""
+    with GraphNorm / activation / dropout between them and optional JK concatenation.  live_edge_weight: handed to every
+    layer (GLASSConv: the aggregation reads the edge weights of each call and is differentiable in them)."""
     def __init__(self, hidden_channels, output_channels, num_layers, max_deg, dropout=0, activation=nn.ReLU(),
-                 conv=GLASSConv, gn=True, jk=False, **kwargs):
+                 conv=GLASSConv, gn=True, jk=False, live_edge_weight=False, **kwargs):
         super().__init__()
+        if live_edge_weight:
+            kwargs["live_edge_weight"] = True
         self.input_emb = nn.Embedding(int(max_deg) + 1, hidden_channels, scale_grad_by_freq=False)
         self.emb_gn = GraphNorm(hidden_channels)
         self.convs = nn.ModuleList()
@@ -495,9 +521,12 @@ class AttnPool(PoolModule):
 
 
 class GLASS(nn.Module):
-    """EmbZGConv + per-target pooling and prediction heads (`preds[id]`, `pools[id]`)."""
-    def __init__(self, conv: EmbZGConv, preds: nn.ModuleList, pools: nn.ModuleList):
+    """EmbZGConv + per-target pooling and prediction heads (`preds[id]`, `pools[id]`).  live_edge_weight=True switches every
+    layer of `conv` to live edge weights (GLASSConv; ValueError for an aggregation that has none)."""
+    def __init__(self, conv: EmbZGConv, preds: nn.ModuleList, pools: nn.ModuleList, live_edge_weight=False):
         super().__init__()
+        if live_edge_weight:
+            set_live_edge_weight(conv)
         self.conv = conv
         self.preds = preds
         self.pools = pools

@@ -274,6 +274,49 @@ def spmm_gat(adj, x, att_src, att_dst, slope=0.2, heads=1):
     return SpMMGatFn.apply(adj, x, att_src, att_dst, slope, int(heads))
 
 
+class SpMMWFn(torch.autograd.Function):
+    """y = A(w) @ x with the values of A a function of the edge weights w (K2's normalisation of aggr "sum" / "mean" / "gcn",
+    CSRAdj.values_of) on the structure of a graph.CSRAdj; backward dx = A(w)^T @ dy on K1 and dw by K1w (csrc/spmm_edge.hip:
+    the sampled dense-dense product, for "gcn" the column sums, then K2's backward, in the caller's edge order).  Each side
+    runs only when its input needs a gradient."""
+    @staticmethod
+    def forward(ctx, adj, x, w):
+        _need_gpu(x)
+        x, _ = _rows(x)
+        val, val_t, deg = adj.values_of(w)
+        ctx.adj = adj
+        ctx.save_for_backward(x, val, val_t, deg)
+        return adj.fwd.spmm(x, val=val)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy, _ = _rows(dy)
+        x, val, val_t, deg = ctx.saved_tensors
+        adj = ctx.adj
+        dx = adj.bwd.spmm(dy, val=val_t) if ctx.needs_input_grad[1] else None
+        dw = None
+        if ctx.needs_input_grad[2]:
+            dval, R = adj.dval(dy, x, val)
+            C = adj.colsum(dval, val_t) if adj.aggr == "gcn" else None
+            dw = adj.values_bwd(dval, R if adj.aggr != "sum" else None, C, None, deg=deg)
+        return None, dx, dw
+
+
+def spmm_w(adj, x, w):
+    """Aggregation at live edge weights: `adj` a graph.CSRAdj built for aggr "sum", "mean" or "gcn" (its structure is used, its
+    stored values are not), w fp32 [E] on the device in the order of the edge_index the adjacency was built from.  The result
+    has the bits ops.spmm gives on an adjacency built from w, and is differentiable in x and in w."""
+    aggr = getattr(adj, "aggr", None)
+    if aggr not in _lib.AGGR_MODES:
+        raise GlassHipError(f"spmm_w: no edge-weight gradient for aggr {aggr!r} (only 'sum', 'mean', 'gcn')")
+    if (not isinstance(w, torch.Tensor) or w.dim() != 1 or w.shape[0] != adj.nnz or w.dtype != torch.float32 or
+            w.device != adj.fwd.rowptr.device):
+        got = f"{tuple(w.shape)} {w.dtype} on {w.device}" if isinstance(w, torch.Tensor) else type(w).__name__
+        raise ValueError(f"spmm_w: w must be {adj.nnz} fp32 on {adj.fwd.rowptr.device} (one per edge, the order of edge_index), "
+                         f"got {got}")
+    return SpMMWFn.apply(adj, x, w)
+
+
 def spmm(adj, x):
     if getattr(adj, "aggr", None) == "max":
         return SpMMMaxFn.apply(adj, x)

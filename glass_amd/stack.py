@@ -587,6 +587,8 @@ class StackProgram:
             # max, softmax and attention aggregation are no products: no fused form, the per-op path (ops.spmm -> K1m,
             # ops.spmm_softmax -> K1s, ops.spmm_gat -> K1a) serves them
             return False
+        if any(getattr(c, "live_edge_weight", False) for c in emb.convs):
+            return False  # live edge weights (ops.spmm_w): the program bakes the adjacency's stored values in
         if isinstance(emb, EmbGConv):
             return StackProgram.supported_unlabeled(emb)
         if not ops.USE_FUSED_DENSE or getattr(emb, "_glass_arena", None) is None or emb.gns is None:

@@ -303,6 +303,42 @@ int glass_gat_datt_mh_f32(const float* X, int64_t ldx, const float* da, const fl
 int glass_adj_values_f32(const int32_t* rowptr, const int32_t* col, const float* w, int64_t n_rows, int aggr,
                          float* deg_ws /*[n_rows], receives deg*/, float* val, void* stream);
 
+/* K1w gradient with respect to the edge weights (an extension: csrc/spmm_edge.hip) of Y = A(w) X for the three aggregations
+ *     of K2, on K1's CSR and plans.  Entry e of row i has column j = col[e]; deg is what K2 left in deg_ws for this w (d~), r =
+ *     d~^(-1/2).
+ *
+ *   glass_spmm_dval_f32: the sampled dense-dense product on the FORWARD CSR: dval[e] = dY[i,:] . X[col[e],:] for every entry
+ *     ([nnz], forward entry order) and, in the same pass, R[i] = sum over the entries of row i of dval[e] val[e] ([n_rows]; 0
+ *     for a row without entries).  12 + 4 H bytes per entry.  ws: glass_spmm_dval_ws_bytes(hdr, H) = one float per partial slot;
+ *     the chunks of a cut row are added by a second launch in slot order.
+ *   glass_adj_colsum_f32: on the TRANSPOSED CSR (row k = column k of A, val_t, eid_t[t] = the forward index of transposed entry
+ *     t, its own plan), no row read: C[k] = sum over the entries t of row k of dval[eid_t[t]] val_t[t] ([n_rows]).  Needed for
+ *     "gcn" only.  ws: glass_adj_colsum_ws_bytes(hdr_t) = one float per partial slot.
+ *   glass_adj_values_bwd_f32: the backward of K2, written in the CALLER's edge order: perm[e] in [0, nnz) is the position, in
+ *     the edge list the CSR was sorted from, of entry e (a permutation; an index outside [0, nnz) is skipped), and
+ *       aggr 1 (sum):  dw[perm[e]] = dval[e]
+ *       aggr 0 (mean): dw[perm[e]] = (dval[e] - R[i]) / deg[i]
+ *       aggr 2 (gcn):  dw[perm[e]] = r_i r_j dval[e] - (R[i] + C[i]) / (2 deg[i])
+ *     (deg, R unused for sum; col, C used for gcn only).  Unknown aggr -> GLASS_E_UNSUPPORTED.
+ *   All: no float atomics, bitwise repeatable for a given plan.  Refused on the host before any launch: null or misaligned
+ *     pointers, H <= 0, ld* < H, partial slots without ws -> GLASS_E_ARG; a header that is no plan for n_rows -> GLASS_E_PLAN; H
+ *     beyond 65535 * 64 columns -> GLASS_E_UNSUPPORTED.  n_rows == 0 returns 0 without a launch.  The *_ws_bytes queries:
+ *     GLASS_E_PLAN for a header that is no plan, GLASS_E_ARG for H <= 0. */
+int64_t glass_spmm_dval_ws_bytes(const int32_t* plan_header_host, int64_t H);
+int glass_spmm_dval_f32(const int32_t* rowptr, const int32_t* col, const float* val,    /* CSR of A */
+                        const float* X, int64_t ldx, const float* dY, int64_t lddy,
+                        float* dval, float* R,                                           /* [nnz], [n_rows] */
+                        int64_t n_rows, int64_t H,
+                        const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_adj_colsum_ws_bytes(const int32_t* plan_t_header_host);
+int glass_adj_colsum_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* val_t, const int32_t* eid_t, /* CSR of A^T */
+                         const float* dval, float* C,                                    /* [nnz], [n_rows] */
+                         int64_t n_rows,
+                         const int32_t* plan_t_header_host, const int32_t* plan_t_dev, void* ws, void* stream);
+int glass_adj_values_bwd_f32(const int32_t* rowptr, const int32_t* col, const int32_t* perm, const float* deg,
+                             const float* dval, const float* R, const float* C, int64_t n_rows, int64_t nnz, int aggr,
+                             float* dw /*[nnz], caller's edge order*/, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * K4  max-zero-one label   replaces utils.MaxZOZ (impl/utils.py:32-45):  z[n]=0; z[pos>=0]=1
  * ---------------------------------------------------------------------------------------- */
