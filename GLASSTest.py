@@ -52,11 +52,12 @@ def parse_args(argv=None):
                         "split's label counts, applied inside the fused loss (default: none)")
     p.add_argument("--pool", type=str, default=None, choices=tuple(POOLS),
                    help="(extension) readout instead of the config file's `pool` (default: the config's value)")
-    p.add_argument("--aggr", type=str, default=None, choices=("mean", "sum", "gcn", "max", "softmax", "gat"),
+    p.add_argument("--aggr", type=str, default=None, choices=("mean", "sum", "gcn", "max", "softmax", "gat", "std", "var"),
                    help="(extension) neighbour aggregation instead of the config file's `aggr` (default: the config's value); "
                         "max: the largest weighted neighbour message per channel; softmax: the softmax-weighted mean of the "
                         "messages with a learned temperature per layer (positive edge weights); gat: attention (--gat_heads heads), "
-                        "the weights from two learned vectors per layer (positive edge weights); none of the three is available "
+                        "the weights from two learned vectors per layer (positive edge weights); std / var: the weighted standard "
+                        "deviation / variance of the messages (positive edge weights); none of the five is available "
                         "with --use_zeroone")
     p.add_argument("--gat_slope", type=float, default=0.2,
                    help="(extension) LeakyReLU's negative slope in the attention scores of --aggr gat (default: 0.2)")

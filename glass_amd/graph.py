@@ -13,7 +13,8 @@ HBM layout (all on the device the graph lives on):
   perm int64[nnz]                                             the build permutation: entry e is the caller's edge perm[e]
 aggr "sum", "mean" and "gcn" can also be evaluated at OTHER edge weights on the same structure, with the gradient with respect
 to them (values_of / dval / colsum / values_bwd: K1w, ops.spmm_w); what that needs beyond perm is built on first use.
-aggr "max", "softmax" and "gat" keep the raw edge weights in val (the values of "sum"); "softmax" and "gat" require them > 0.
+aggr "max", "softmax", "gat", "std" and "var" keep the raw edge weights in val (the values of "sum"); all but "max" require
+them > 0.
 Duplicate (row,col) entries are kept as separate entries: they add up in the product exactly as in
 the reference's uncoalesced COO matmul.
 """
@@ -128,6 +129,8 @@ def _csr_from_sorted(row, n_rows):
 
 
 _ws_branch = 0
+_RAW_AGGR = ("max", "softmax", "gat", "std", "var")  # the extensions: raw edge weights in val, kernels of their own
+MOMENT_KINDS = {"std": 0, "var": 1}
 
 
 def set_workspace_branch(b):
@@ -142,10 +145,13 @@ class CSRAdj:
     extension): the raw weights too, strictly positive (checked here, once), aggregated by K1s (softmax_fwd / softmax_bwd /
     softmax_dt) with a temperature the caller owns.  aggr "gat" (an extension): built like "softmax", aggregated by K1a
     (gat_scores / gat_fwd / gat_edge / gat_bwd / gat_datt, each with heads=K for multi-head attention) with two attention
-    vectors the caller owns."""
+    vectors the caller owns.  aggr "std" / "var" (extensions): built like "softmax", aggregated by K1v (moment_fwd /
+    moment_bwd: the weighted standard deviation or variance of the neighbour messages, with their weighted mean)."""
     def __init__(self, edge_index, edge_weight, n_node, aggr):
-        if aggr not in _lib.AGGR_MODES and aggr not in ("max", "softmax", "gat"):
+        if aggr not in _lib.AGGR_MODES and aggr not in _RAW_AGGR:
             raise NotImplementedError  # same error type as the reference (models.py:110-111)
+        if aggr in MOMENT_KINDS and not bool((edge_weight > 0).all()):  # one read; the kernels do not test it
+            raise ValueError(f"aggr {aggr!r}: edge weights are multiplicities and must be strictly positive")
         if not edge_index.is_cuda:
             raise _lib.GlassHipError("glass_amd runs on the GPU only (edge_index is on %s); the CPU path lives in "
                                      "oracle/ as a checker, not as a fallback" % edge_index.device)
@@ -165,7 +171,7 @@ class CSRAdj:
         self.deg = torch.empty(n, dtype=torch.float32, device=dev)
         val = torch.empty(nnz, dtype=torch.float32, device=dev)
         rc = _lib.load().glass_adj_values_f32(rowptr.data_ptr(), col32.data_ptr(), w.data_ptr(), n,
-                                              _lib.AGGR_MODES["sum" if aggr in ("max", "softmax", "gat") else aggr], self.deg.data_ptr(),
+                                              _lib.AGGR_MODES["sum" if aggr in _RAW_AGGR else aggr], self.deg.data_ptr(),
                                               val.data_ptr(),
                                               torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "glass_adj_values_f32")
@@ -180,7 +186,7 @@ class CSRAdj:
         self.bwd = CSROperand(rowptr_t, col_t, val_t, n, n)
         if aggr in ("max", "gat"):
             self.eid_t = perm_t.to(torch.int32).contiguous()  # transposed entry t is forward entry eid_t[t]
-        if aggr in ("max", "softmax", "gat"):
+        if aggr in _RAW_AGGR:
             self._aggr_ws = {}
             self._retired_ws = []
 
@@ -189,7 +195,7 @@ class CSRAdj:
         return self.fwd.nnz
 
     def _aggr_workspace(self, entry, H, nbytes):
-        """Workspaces of K1m, K1s and K1a (partial pairs / triples / rows of cut rows, the fp64 partials of "softmax_dt" and "gat_datt"): one
+        """Workspaces of K1m, K1s, K1a and K1v (partial pairs / triples / rows of cut rows, the fp64 partials of "softmax_dt" and "gat_datt"): one
         8-byte aligned buffer per entry, feature width and branch (set_workspace_branch)."""
         if nbytes < 0:
             raise _lib.GlassHipError("bad plan header")
@@ -408,6 +414,53 @@ class CSRAdj:
                                            ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "glass_spmm_softmax_dt_f32")
         return dt
+
+    def _need_moment(self, what):
+        if self.aggr not in MOMENT_KINDS:
+            raise _lib.GlassHipError(f"CSRAdj.{what}: this adjacency was built for aggr {self.aggr!r}, not 'std' or 'var'")
+
+    def moment_fwd(self, x, kind=None, eps=1e-5):
+        """(s, mu, wsum) = K1v forward: per destination and channel the weighted standard deviation sqrt(var + eps) (kind "std")
+        or variance (kind "var"; None: the adjacency's own aggr) of the neighbour messages, their weighted mean, and per
+        destination the sum of its weights; zeros for a row without entries."""
+        self._need_moment("moment_fwd")
+        kind = self.aggr if kind is None else kind
+        if kind not in MOMENT_KINDS:
+            raise ValueError(f"moment_fwd: kind must be 'std' or 'var', not {kind!r}")
+        op = self.fwd
+        ldx = self._softmax_operand(x, op.n_cols, "X")
+        H = x.shape[1]
+        lib = _lib.load()
+        s = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
+        mu = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
+        wsum = torch.empty(op.n_rows, dtype=torch.float32, device=x.device)
+        ws = self._aggr_workspace("moment_fwd", H, lib.glass_spmm_moment_ws_bytes(op.header.ctypes.data, H))
+        rc = lib.glass_spmm_moment_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
+                                           float(eps), MOMENT_KINDS[kind], s.data_ptr(), H, mu.data_ptr(), H, wsum.data_ptr(),
+                                           op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
+                                           torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_moment_csr_f32")
+        return s, mu, wsum
+
+    def moment_bwd(self, x, mu, A, C=None):
+        """dx of K1v from the forward's operand x, its mean mu and the caller's per-destination factors A and C (None: the mean
+        carries no gradient): dx[j] = sum over the entries (destination i) of val * (C[i] + A[i] * (x[j] - mu[i]))."""
+        self._need_moment("moment_bwd")
+        op = self.bwd
+        ldx = self._softmax_operand(x, op.n_rows, "X")
+        ldmu, lda = (self._softmax_operand(a, op.n_cols, n) for a, n in ((mu, "Mu"), (A, "A")))
+        ldc = 0 if C is None else self._softmax_operand(C, op.n_cols, "C")
+        assert x.shape == mu.shape == A.shape and (C is None or C.shape == x.shape)
+        H = x.shape[1]
+        lib = _lib.load()
+        dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
+        ws = self._aggr_workspace("moment_bwd", H, lib.glass_spmm_moment_bwd_ws_bytes(op.header.ctypes.data, H))
+        rc = lib.glass_spmm_moment_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
+                                           mu.data_ptr(), ldmu, A.data_ptr(), lda, None if C is None else C.data_ptr(), ldc,
+                                           dx.data_ptr(), H, op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
+                                           ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_moment_bwd_f32")
+        return dx
 
     def _need_gat(self, what):
         if self.aggr != "gat":

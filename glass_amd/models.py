@@ -9,7 +9,8 @@ Reference map (file:line under /root/reference):
   PoolModule/AddPool/MaxPool/MeanPool/SizePool 275-319 · GLASS 322-355   (impl/models.py)
 Not in the reference: AttnPool (attention readout, pool "attn"); aggr "max" (max neighbour aggregation, buildAdj); aggr
 "softmax" (softmax neighbour aggregation with a learned temperature: the conv layers' parameter `t`); aggr "gat" (attention
-aggregation with `gat_heads` heads: GLASSConv's parameters `att_src` and `att_dst`).
+aggregation with `gat_heads` heads: GLASSConv's parameters `att_src` and `att_dst`); aggr "std" / "var" (the weighted standard
+deviation / variance of the neighbour messages, GLASSConv only: no parameter, the constant `moment_eps`).
 """
 import math
 
@@ -148,8 +149,9 @@ def buildAdj(edge_index, edge_weight, n_node: int, aggr: str):
     reference's COO.  One instance is shared by every layer asking for the same (graph, aggr) —
     the reference builds an identical copy per layer (models.py:154-156).  aggr "max" (an extension): the raw weights,
     aggregated by ops.spmm with a max instead of a sum.  aggr "softmax" (an extension): the raw weights, strictly positive
-    (ValueError otherwise), aggregated by ops.spmm_softmax with the layer's temperature."""
-    if aggr not in ("mean", "sum", "gcn", "max", "softmax", "gat"):  # ("gat", an extension: built like "softmax", ops.spmm_gat)
+    (ValueError otherwise), aggregated by ops.spmm_softmax with the layer's temperature.  aggr "std" / "var" (extensions): built
+    like "softmax", aggregated by ops.spmm_moments."""
+    if aggr not in ("mean", "sum", "gcn", "max", "softmax", "gat", "std", "var"):  # ("gat", an extension: built like "softmax", ops.spmm_gat)
         raise NotImplementedError
     for ei, ew, n, a, adj in _adj_cache:
         if ei is edge_index and ew is edge_weight and n == int(n_node) and a == aggr:
@@ -198,9 +200,12 @@ class GLASSConv(nn.Module):
     live_edge_weight (an extension, aggr "sum" / "mean" / "gcn" only: ValueError otherwise): the layer aggregates with the
     `edge_weight` of EACH call (ops.spmm_w: the normalisation is evaluated again, and the result is differentiable in the
     weights) on the structure cached from the first call; no parameter, the same state_dict.  Such a layer runs as per-op
-    autograd nodes: the stack program (stack.StackProgram, the captured step program of step.TrainStep) declines its model."""
+    autograd nodes: the stack program (stack.StackProgram, the captured step program of step.TrainStep) declines its model.
+    aggr "std" / "var" (extensions): the layer aggregates with the weighted standard deviation sqrt(Var + moment_eps) or the
+    weighted variance of the mixed messages (ops.spmm_moments' first result: the widths do not change); no parameter, the
+    state_dict of aggr "mean"; one graph at a time (ValueError with `batch` or live_edge_weight)."""
     def __init__(self, in_channels: int, out_channels: int, activation=nn.ReLU(inplace=True), aggr="mean",
-                 z_ratio=0.8, dropout=0.2, softmax_t=1.0, gat_slope=0.2, gat_heads=1, live_edge_weight=False):
+                 z_ratio=0.8, dropout=0.2, softmax_t=1.0, gat_slope=0.2, gat_heads=1, live_edge_weight=False, moment_eps=1e-5):
         super().__init__()
         if live_edge_weight and aggr not in ("sum", "mean", "gcn"):
             raise ValueError(f"GLASSConv: live_edge_weight needs aggr 'sum', 'mean' or 'gcn', not {aggr!r} (no edge-weight "
@@ -219,6 +224,7 @@ class GLASSConv(nn.Module):
         self.softmax_t = float(softmax_t)
         if aggr == "softmax":  # (no other configuration owns the key: their state_dict is unchanged)
             self.t = nn.Parameter(torch.full((1, ), self.softmax_t))
+        self.moment_eps = float(moment_eps)
         self.gat_slope = float(gat_slope)
         self.gat_heads = gat_heads
         if aggr == "gat":  # (likewise: only this configuration owns the two keys)
@@ -245,6 +251,8 @@ class GLASSConv(nn.Module):
         calls key only on the row's label byte and take the R * N rows as they are."""
         if self.live_edge_weight and batch is not None:
             raise ValueError("GLASSConv: live_edge_weight has no replicated form (exact zero-one labels: `batch` given)")
+        if self.aggr in ("std", "var") and batch is not None:
+            raise ValueError(f"GLASSConv: aggr {self.aggr!r} has no replicated form (exact zero-one labels: `batch` given)")
         if self.adj is None:
             self.adj = buildAdj(edge_index, edge_weight.detach() if self.live_edge_weight else edge_weight,
                                 x_.shape[0] if batch is None else batch.N, self.aggr)
@@ -258,6 +266,8 @@ class GLASSConv(nn.Module):
             agg = lambda m: ops.spmm_softmax(self.adj, m, self.t)
         elif self.aggr == "gat":
             agg = lambda m: ops.spmm_gat(self.adj, m, self.att_src, self.att_dst, self.gat_slope, self.gat_heads)
+        elif self.aggr in ("std", "var"):
+            agg = lambda m: ops.spmm_moments(self.adj, m, self.aggr, self.moment_eps)[0]
         else:
             agg = lambda m: ops.spmm(self.adj, m)
         rep = {} if batch is None else {"rep": batch}  # (a training pass collects the weight gradients replica by replica)

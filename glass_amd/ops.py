@@ -213,6 +213,60 @@ def spmm_softmax(adj, x, t):
     return SpMMSoftmaxFn.apply(adj, x, t)
 
 
+class SpMMMomentFn(torch.autograd.Function):
+    """(s, mu) = the weighted standard deviation (or variance) and mean of the messages x[col] over the entries of row i of A
+    (aggr "std" / "var", K1v: csrc/spmm_moment.hip).  The node keeps x, s, mu and the rows' weight sums; the backward is one
+    transposed pass, which reads the mean's factor only when mu's gradient was asked for (A carries no gradient)."""
+    @staticmethod
+    def forward(ctx, adj, x, kind, eps):
+        _need_gpu(x)
+        x, _ = _rows(x)
+        s, mu, wsum = adj.moment_fwd(x, kind, eps)
+        ctx.adj, ctx.kind = adj, kind
+        ctx.save_for_backward(x, s, mu, wsum)
+        ctx.set_materialize_grads(False)  # a result nobody used arrives as None, not as zeros: C is then not formed
+        return s, mu
+
+    @staticmethod
+    def backward(ctx, ds, dmu):
+        if not ctx.needs_input_grad[1] or (ds is None and dmu is None):
+            return None, None, None, None
+        x, s, mu, wsum = ctx.saved_tensors
+        A, C = moment_factors(ctx.kind, s, wsum, ds, dmu)
+        return None, ctx.adj.moment_bwd(x, mu, A, C), None, None
+
+
+def moment_factors(kind, s, wsum, ds, dmu=None):
+    """(A, C) of K1v's backward from the forward's results and the gradients of S and Mu (either may be None) — per destination,
+    N * H work: std: A = dS / (W S); var: A = 2 dS / W; C = dMu / W (None without dMu); a row without entries gives 0."""
+    w = wsum[:, None]
+    live = w > 0
+    one = torch.ones((), dtype=s.dtype, device=s.device)
+    if ds is None:
+        A = torch.zeros_like(s)
+    else:
+        ds, _ = _rows(ds)
+        den = w * s if kind == "std" else (0.5 * w).expand_as(s)
+        A = torch.where(live, ds / torch.where(live, den, one), torch.zeros_like(ds)).contiguous()
+    C = None
+    if dmu is not None:
+        dmu, _ = _rows(dmu)
+        C = torch.where(live, dmu / torch.where(live, w, one), torch.zeros_like(dmu)).contiguous()
+    return A, C
+
+
+def spmm_moments(adj, x, kind="std", eps=1e-5):
+    """Spread of the neighbour messages: `adj` a graph.CSRAdj built for aggr "std" or "var".  Returns (S, Mu): per destination
+    and channel the weighted standard deviation sqrt(Var + eps) (kind "std") or the weighted variance (kind "var"), and the
+    weighted mean; zeros for a node without in-edges.  Differentiable in x through both results; under no_grad, or when x needs
+    no gradient, nothing of the backward is launched."""
+    if getattr(adj, "aggr", None) not in ("std", "var"):
+        raise GlassHipError(f"spmm_moments: the adjacency was built for aggr {getattr(adj, 'aggr', None)!r}, not 'std' or 'var'")
+    if kind not in ("std", "var"):
+        raise ValueError(f"spmm_moments: kind must be 'std' or 'var', not {kind!r}")
+    return SpMMMomentFn.apply(adj, x, kind, float(eps))
+
+
 def _heads_kw(heads):
     """heads == 1 calls the CSRAdj methods exactly as before the argument existed"""
     return {} if heads == 1 else {"heads": heads}
@@ -325,6 +379,8 @@ def spmm(adj, x):
     if getattr(adj, "aggr", None) == "gat":
         raise GlassHipError("spmm: a gat adjacency has no attention vectors of its own; call "
                             "ops.spmm_gat(adj, x, att_src, att_dst, slope)")
+    if getattr(adj, "aggr", None) in ("std", "var"):
+        raise GlassHipError(f"spmm: a {adj.aggr} adjacency is no product; call ops.spmm_moments(adj, x, kind, eps)")
     return SpMMFn.apply(adj, x)
 
 
@@ -1144,6 +1200,9 @@ def spmm_rep(adj, x, R):
                             "zero-one labels / --use_zeroone with it)")
     if getattr(adj, "aggr", None) == "gat":
         raise GlassHipError("replicated gat aggregation is not built: aggr 'gat' runs one graph at a time (no exact "
+                            "zero-one labels / --use_zeroone with it)")
+    if getattr(adj, "aggr", None) in ("std", "var"):
+        raise GlassHipError(f"replicated {adj.aggr} aggregation is not built: aggr '{adj.aggr}' runs one graph at a time (no exact "
                             "zero-one labels / --use_zeroone with it)")
     return SpMMRepFn.apply(adj, x, int(R))
 

@@ -182,6 +182,48 @@ int glass_spmm_softmax_dt_f32(const int32_t* rowptr, const int32_t* col, const f
                               int64_t n_rows, int64_t H,
                               const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
 
+/* K1v standard-deviation and variance neighbour aggregation (aggr "std" / "var": an extension, the reference has none; PNA,
+ *     PyG's StdAggregation / VarAggregation) at the call site K1 serves, `self.adj @ x` (impl/models.py:164), on K1's CSR and
+ *     plans.  Forward CSR as for K1s: entries sorted by (row, col), stable, duplicates kept (two entries), row = destination;
+ *     val = the raw edge weights, which act as multiplicities and must be > 0 (the caller's check: the kernels do not test it).
+ *
+ *   glass_spmm_moment_csr_f32: over the entries e of row i, x_e = X[col[e],c], w_e = val[e]:
+ *         W = sum_e w_e     Mu = sum_e w_e x_e / W     Var = sum_e w_e (x_e - Mu)^2 / W     Std = sqrt(Var + eps)
+ *     S[i,c] = Std (kind 0) or Var (kind 1), Mu[i,c], Wsum[i] = W.  A row without entries: S = Mu = Wsum = 0.  One pass, every
+ *     source row gathered once.  The state is the triple (W, mean, M2); an entry is (w, x, 0); entries, lane groups, the four
+ *     waves of a long-row item and the chunks of a cut row merge with Chan's update
+ *         d = m_b - m_a,  W = W_a + W_b,  m = m_a + d W_b / W,  M2 = M2_a + M2_b + d^2 W_a W_b / W   (an empty side: identity)
+ *     in a fixed order: bitwise repeatable for a given plan (not identical across plans).  No x^2 is formed: a row whose
+ *     messages are all equal has Var == 0 exactly (Std == sqrt(eps)).  ws: glass_spmm_moment_ws_bytes(hdr, H) = the plan's
+ *     partial slots times (2 H + 1) floats; cut rows are merged by a second launch in slot order.
+ *   glass_spmm_moment_bwd_f32: on the TRANSPOSED CSR (row j = source, col_t = destinations i, val_t, its own plan):
+ *         dX[j,c] = sum over the entries of row j of val_t * (C[i,c] + A[i,c] * (X[j,c] - Mu[i,c]))
+ *     with A, C [n, H] from the caller — std: A = dS / (Wsum S); var: A = 2 dS / Wsum; C = dMu / Wsum; 0 where Wsum = 0.  C may
+ *     be null (Mu carries no gradient): its rows are then not read.  X - Mu is formed per entry, never factored out of the sum;
+ *     fixed order, no float atomics, bitwise repeatable.  Row j's own X row is read once; per entry two [H] rows of the
+ *     destination (A, Mu), three with C.  ws: glass_spmm_moment_bwd_ws_bytes(hdr_t, H).
+ *   Both: every H and leading dimension K1s takes (16-byte vector form when H, the ld* and the pointers allow it, scalar form
+ *     otherwise).  Refused on the host before any launch: null or misaligned pointers, H <= 0, ld* < H, a kind other than 0 / 1,
+ *     eps < 0, partial slots without ws -> GLASS_E_ARG; a header that is no plan for n_rows -> GLASS_E_PLAN; H beyond
+ *     65535 * 64 columns -> GLASS_E_UNSUPPORTED.  n_rows == 0 returns 0 without a launch.  The *_ws_bytes queries:
+ *     GLASS_E_PLAN for a header that is no plan, GLASS_E_ARG for H <= 0. */
+int64_t glass_spmm_moment_ws_bytes(const int32_t* plan_header_host, int64_t H);
+int glass_spmm_moment_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val, /* CSR of A, device */
+                              const float* X, int64_t ldx,                                 /* [n_cols, H] */
+                              float eps, int kind,                                         /* 0 = std, 1 = var */
+                              float* S, int64_t lds, float* Mu, int64_t ldmu,              /* [n_rows, H] each */
+                              float* Wsum,                                                 /* [n_rows] */
+                              int64_t n_rows, int64_t H,
+                              const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_spmm_moment_bwd_ws_bytes(const int32_t* plan_t_header_host, int64_t H);
+int glass_spmm_moment_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* val_t,   /* CSR of A^T */
+                              const float* X, int64_t ldx,                                         /* [n_rows, H] */
+                              const float* Mu, int64_t ldmu, const float* A, int64_t lda,          /* [n_cols of A^T, H] each */
+                              const float* C, int64_t ldc,                                         /* likewise, or null */
+                              float* dX, int64_t lddx,                                             /* [n_rows, H] */
+                              int64_t n_rows, int64_t H,
+                              const int32_t* plan_t_header_host, const int32_t* plan_t_dev, void* ws, void* stream);
+
 /* K1a attention neighbour aggregation (aggr "gat": an extension, the reference has none; single-head GAT) at the call site K1
  *     serves, on K1's CSR and plans.  Forward CSR as for K1s (raw weights > 0, multiplicities; the caller's check).  att_src,
  *     att_dst: two [H] fp32 vectors in device memory; slope: LeakyReLU's negative slope, by value.  With
