@@ -52,12 +52,14 @@ def parse_args(argv=None):
                         "split's label counts, applied inside the fused loss (default: none)")
     p.add_argument("--pool", type=str, default=None, choices=tuple(POOLS),
                    help="(extension) readout instead of the config file's `pool` (default: the config's value)")
-    p.add_argument("--aggr", type=str, default=None, choices=("mean", "sum", "gcn", "max", "softmax", "gat", "std", "var"),
+    p.add_argument("--aggr", type=str, default=None, choices=("mean", "sum", "gcn", "max", "softmax", "gat", "std", "var", "pna"),
                    help="(extension) neighbour aggregation instead of the config file's `aggr` (default: the config's value); "
                         "max: the largest weighted neighbour message per channel; softmax: the softmax-weighted mean of the "
                         "messages with a learned temperature per layer (positive edge weights); gat: attention (--gat_heads heads), "
                         "the weights from two learned vectors per layer (positive edge weights); std / var: the weighted standard "
-                        "deviation / variance of the messages (positive edge weights); none of the five is available "
+                        "deviation / variance of the messages (positive edge weights); pna: mean, max, min and standard deviation of the "
+                        "messages under three degree scalers, mixed per channel by a learned [12, hidden] weight per layer "
+                        "(positive edge weights); none of the six is available "
                         "with --use_zeroone")
     p.add_argument("--gat_slope", type=float, default=0.2,
                    help="(extension) LeakyReLU's negative slope in the attention scores of --aggr gat (default: 0.2)")

@@ -86,6 +86,12 @@ SIGNATURES = {
     "glass_spmm_moment_csr_f32": (c_int, [_P, _P, _P, _P, _I, c_float, c_int, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
     "glass_spmm_moment_bwd_ws_bytes": (c_int64, [_P, _I]),
     "glass_spmm_moment_bwd_f32": (c_int, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "glass_spmm_pna_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_pna_csr_f32": (c_int, [_P, _P, _P, _P, _I, c_float, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _P,
+                                       _P, _P, _P]),
+    "glass_spmm_pna_bwd_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_pna_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I,
+                                       _I, _P, _P, _P, _P]),
     "glass_gat_scores_f32": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _P]),
     "glass_spmm_gat_ws_bytes": (c_int64, [_P, _I]),
     "glass_spmm_gat_csr_f32": (c_int, [_P, _P, _P, _P, _I, _P, _P, c_float, _P, _I, _P, _I, _I, _P, _P, _P, _P]),

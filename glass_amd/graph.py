@@ -9,12 +9,12 @@ HBM layout (all on the device the graph lives on):
   rowptr int32[N+1], col int32[nnz], val fp32[nnz]            CSR of A   (row = destination)
   rowptr_t, col_t, val_t                                      CSR of A^T (for the backward)
   plan / plan_t int32[...]                                    opaque K1 schedules
-  eid_t int32[nnz]                                            aggr "max" and "gat": forward index of each entry of A^T
+  eid_t int32[nnz]                                            aggr "max", "gat" and "pna": forward index of each entry of A^T
   perm int64[nnz]                                             the build permutation: entry e is the caller's edge perm[e]
 aggr "sum", "mean" and "gcn" can also be evaluated at OTHER edge weights on the same structure, with the gradient with respect
 to them (values_of / dval / colsum / values_bwd: K1w, ops.spmm_w); what that needs beyond perm is built on first use.
-aggr "max", "softmax", "gat", "std" and "var" keep the raw edge weights in val (the values of "sum"); all but "max" require
-them > 0.
+aggr "max", "softmax", "gat", "std", "var" and "pna" keep the raw edge weights in val (the values of "sum"); all but "max"
+require them > 0.
 Duplicate (row,col) entries are kept as separate entries: they add up in the product exactly as in
 the reference's uncoalesced COO matmul.
 """
@@ -128,8 +128,21 @@ def _csr_from_sorted(row, n_rows):
     return rowptr.to(torch.int32)
 
 
+def _pna_degrees(rowptr, w):
+    """(delta, wsum) of PNA's degree scalers, in fp64 on the host (once, at build): W_i the weight sum of row i (the weights
+    are positive, so a row with entries has W > 0); delta the mean over the rows with entries of log(W_i + 1), 1.0 when no
+    row has entries; wsum the W_i rounded to fp32, on the graph's device."""
+    rp = rowptr.cpu().numpy().astype(np.int64)
+    live = rp[1:] > rp[:-1]
+    W = np.zeros(rp.shape[0] - 1, dtype=np.float64)
+    if live.any():
+        W[live] = np.add.reduceat(w.double().cpu().numpy(), rp[:-1][live])
+    delta = float(np.log1p(W[live]).mean()) if live.any() else 1.0
+    return delta, torch.from_numpy(W.astype(np.float32)).to(rowptr.device)
+
+
 _ws_branch = 0
-_RAW_AGGR = ("max", "softmax", "gat", "std", "var")  # the extensions: raw edge weights in val, kernels of their own
+_RAW_AGGR = ("max", "softmax", "gat", "std", "var", "pna")  # the extensions: raw edge weights in val, kernels of their own
 MOMENT_KINDS = {"std": 0, "var": 1}
 
 
@@ -146,11 +159,15 @@ class CSRAdj:
     softmax_dt) with a temperature the caller owns.  aggr "gat" (an extension): built like "softmax", aggregated by K1a
     (gat_scores / gat_fwd / gat_edge / gat_bwd / gat_datt, each with heads=K for multi-head attention) with two attention
     vectors the caller owns.  aggr "std" / "var" (extensions): built like "softmax", aggregated by K1v (moment_fwd /
-    moment_bwd: the weighted standard deviation or variance of the neighbour messages, with their weighted mean)."""
+    moment_bwd: the weighted standard deviation or variance of the neighbour messages, with their weighted mean).  aggr "pna"
+    (an extension): built like "softmax", aggregated by K1p (pna_fwd / pna_bwd: mean, standard deviation, max and min of the
+    neighbour messages from one gather); `pna_delta` is the mean of log(W_i + 1) over the rows with entries (PNA's degree
+    normaliser, a Python float from fp64 arithmetic at build; 1.0 for a graph without entries) and `pna_wsum` [N] the W_i
+    it was formed from, rounded to fp32 (what ops.pna_mix scales with)."""
     def __init__(self, edge_index, edge_weight, n_node, aggr):
         if aggr not in _lib.AGGR_MODES and aggr not in _RAW_AGGR:
             raise NotImplementedError  # same error type as the reference (models.py:110-111)
-        if aggr in MOMENT_KINDS and not bool((edge_weight > 0).all()):  # one read; the kernels do not test it
+        if (aggr in MOMENT_KINDS or aggr == "pna") and not bool((edge_weight > 0).all()):  # one read; the kernels do not test it
             raise ValueError(f"aggr {aggr!r}: edge weights are multiplicities and must be strictly positive")
         if not edge_index.is_cuda:
             raise _lib.GlassHipError("glass_amd runs on the GPU only (edge_index is on %s); the CPU path lives in "
@@ -184,18 +201,20 @@ class CSRAdj:
         self.perm = perm  # entry e of the forward CSR is edge perm[e] of the caller's edge_index (int64, as argsort left it)
         self.fwd = CSROperand(rowptr, col32, val, n, n)
         self.bwd = CSROperand(rowptr_t, col_t, val_t, n, n)
-        if aggr in ("max", "gat"):
+        if aggr in ("max", "gat", "pna"):
             self.eid_t = perm_t.to(torch.int32).contiguous()  # transposed entry t is forward entry eid_t[t]
         if aggr in _RAW_AGGR:
             self._aggr_ws = {}
             self._retired_ws = []
+        if aggr == "pna":
+            self.pna_delta, self.pna_wsum = _pna_degrees(rowptr, w)
 
     @property
     def nnz(self):
         return self.fwd.nnz
 
     def _aggr_workspace(self, entry, H, nbytes):
-        """Workspaces of K1m, K1s, K1a and K1v (partial pairs / triples / rows of cut rows, the fp64 partials of "softmax_dt" and "gat_datt"): one
+        """Workspaces of K1m, K1s, K1a, K1v and K1p (partial pairs / triples / rows of cut rows, the fp64 partials of "softmax_dt" and "gat_datt"): one
         8-byte aligned buffer per entry, feature width and branch (set_workspace_branch)."""
         if nbytes < 0:
             raise _lib.GlassHipError("bad plan header")
@@ -460,6 +479,57 @@ class CSRAdj:
                                            dx.data_ptr(), H, op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
                                            ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "glass_spmm_moment_bwd_f32")
+        return dx
+
+    def _need_pna(self, what):
+        if self.aggr != "pna":
+            raise _lib.GlassHipError(f"CSRAdj.{what}: this adjacency was built for aggr {self.aggr!r}, not 'pna'")
+
+    def pna_fwd(self, x, eps=1e-5):
+        """(mu, s, mx, mn, amx, amn, wsum) = K1p forward, one gather of every source row: per destination and channel the
+        weighted mean and standard deviation sqrt(var + eps) of the neighbour messages, their largest and smallest with the
+        winning entries (int32, -1 for a row without entries), and per destination the sum of its weights; zeros for a row
+        without entries."""
+        self._need_pna("pna_fwd")
+        op = self.fwd
+        ldx = self._softmax_operand(x, op.n_cols, "X")
+        H = x.shape[1]
+        lib = _lib.load()
+        mu, s, mx, mn = (torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device) for _ in range(4))
+        amx, amn = (torch.empty((op.n_rows, H), dtype=torch.int32, device=x.device) for _ in range(2))
+        wsum = torch.empty(op.n_rows, dtype=torch.float32, device=x.device)
+        ws = self._aggr_workspace("pna_fwd", H, lib.glass_spmm_pna_ws_bytes(op.header.ctypes.data, H))
+        rc = lib.glass_spmm_pna_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx, float(eps),
+                                        mu.data_ptr(), H, s.data_ptr(), H, mx.data_ptr(), H, mn.data_ptr(), H, amx.data_ptr(), H,
+                                        amn.data_ptr(), H, wsum.data_ptr(), op.n_rows, H, op.header.ctypes.data,
+                                        op.plan.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_pna_csr_f32")
+        return mu, s, mx, mn, amx, amn, wsum
+
+    def pna_bwd(self, x, mu, A, C, amx, gmx, amn, gmn):
+        """dx of K1p from the forward's operand x, its mean mu and winners amx / amn, and the caller's per-destination rows A, C
+        (ops.pna_factors), gmx and gmn (all required: zeros for a result without a gradient):
+        dx[j] = sum over the entries (destination i) of val * (C[i] + A[i] * (x[j] - mu[i])) + gmx[i] where this entry won
+        the max + gmn[i] where it won the min."""
+        self._need_pna("pna_bwd")
+        op = self.bwd
+        ldx = self._softmax_operand(x, op.n_rows, "X")
+        ldmu, lda, ldc, ldgx, ldgn = (self._softmax_operand(a, op.n_cols, n)
+                                      for a, n in ((mu, "Mu"), (A, "A"), (C, "C"), (gmx, "Gmx"), (gmn, "Gmn")))
+        for a in (amx, amn):
+            assert a.dtype == torch.int32 and a.dim() == 2 and a.stride(1) == 1 and a.is_cuda and a.shape == x.shape
+        assert x.shape == mu.shape == A.shape == C.shape == gmx.shape == gmn.shape
+        H = x.shape[1]
+        ldax, ldan = (a.stride(0) if a.shape[0] > 1 else max(H, a.stride(0)) for a in (amx, amn))
+        lib = _lib.load()
+        dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
+        ws = self._aggr_workspace("pna_bwd", H, lib.glass_spmm_pna_bwd_ws_bytes(op.header.ctypes.data, H))
+        rc = lib.glass_spmm_pna_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
+                                        x.data_ptr(), ldx, mu.data_ptr(), ldmu, A.data_ptr(), lda, C.data_ptr(), ldc,
+                                        amx.data_ptr(), ldax, gmx.data_ptr(), ldgx, amn.data_ptr(), ldan, gmn.data_ptr(), ldgn,
+                                        dx.data_ptr(), H, op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
+                                        ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "glass_spmm_pna_bwd_f32")
         return dx
 
     def _need_gat(self, what):

@@ -10,7 +10,9 @@ Reference map (file:line under /root/reference):
 Not in the reference: AttnPool (attention readout, pool "attn"); aggr "max" (max neighbour aggregation, buildAdj); aggr
 "softmax" (softmax neighbour aggregation with a learned temperature: the conv layers' parameter `t`); aggr "gat" (attention
 aggregation with `gat_heads` heads: GLASSConv's parameters `att_src` and `att_dst`); aggr "std" / "var" (the weighted standard
-deviation / variance of the neighbour messages, GLASSConv only: no parameter, the constant `moment_eps`).
+deviation / variance of the neighbour messages, GLASSConv only: no parameter, the constant `moment_eps`); aggr "pna" (PNA:
+mean, max, min and standard deviation of the neighbour messages under three degree scalers, GLASSConv only: its parameter
+`pna_weight` [12, out_channels], the constant `moment_eps`).
 """
 import math
 
@@ -150,8 +152,9 @@ def buildAdj(edge_index, edge_weight, n_node: int, aggr: str):
     the reference builds an identical copy per layer (models.py:154-156).  aggr "max" (an extension): the raw weights,
     aggregated by ops.spmm with a max instead of a sum.  aggr "softmax" (an extension): the raw weights, strictly positive
     (ValueError otherwise), aggregated by ops.spmm_softmax with the layer's temperature.  aggr "std" / "var" (extensions): built
-    like "softmax", aggregated by ops.spmm_moments."""
-    if aggr not in ("mean", "sum", "gcn", "max", "softmax", "gat", "std", "var"):  # ("gat", an extension: built like "softmax", ops.spmm_gat)
+    like "softmax", aggregated by ops.spmm_moments.  aggr "pna" (an extension): built like "softmax", aggregated by
+    ops.spmm_pna / ops.pna_mix."""
+    if aggr not in ("mean", "sum", "gcn", "max", "softmax", "gat", "std", "var", "pna"):  # ("gat", an extension: built like "softmax", ops.spmm_gat)
         raise NotImplementedError
     for ei, ew, n, a, adj in _adj_cache:
         if ei is edge_index and ew is edge_weight and n == int(n_node) and a == aggr:
@@ -180,6 +183,13 @@ def _reset_gat_att(conv):
             conv.att_dst.uniform_(-bound, bound)
 
 
+def _reset_pna_weight(conv):
+    """The twelve views of a conv layer with aggr "pna" back to equal shares (in place: the parameter may live in an arena)."""
+    if conv.aggr == "pna":
+        with torch.no_grad():
+            conv.pna_weight.fill_(1.0 / 12.0)
+
+
 def set_live_edge_weight(emb):
     """Every GLASSConv layer of `emb` to live edge weights (what their constructor argument sets)."""
     for c in emb.convs:
@@ -203,7 +213,13 @@ class GLASSConv(nn.Module):
     autograd nodes: the stack program (stack.StackProgram, the captured step program of step.TrainStep) declines its model.
     aggr "std" / "var" (extensions): the layer aggregates with the weighted standard deviation sqrt(Var + moment_eps) or the
     weighted variance of the mixed messages (ops.spmm_moments' first result: the widths do not change); no parameter, the
-    state_dict of aggr "mean"; one graph at a time (ValueError with `batch` or live_edge_weight)."""
+    state_dict of aggr "mean"; one graph at a time (ValueError with `batch` or live_edge_weight).
+    aggr "pna" (an extension, PNA): the layer aggregates with ops.pna_mix of ops.spmm_pna's four results — mean, max, min and
+    standard deviation sqrt(Var + moment_eps) of the mixed messages, each under the scalers 1, log(W + 1) / delta and
+    delta / log(W + 1) (W the node's weight sum, delta the graph's mean of log(W + 1)), the twelve views weighted per channel
+    by the layer's parameter pna_weight [12, out_channels] (1 / 12 each at the start: the widths do not change, and PNA's
+    dense post-tower is the comb pair this layer already has).  The state_dict is that of aggr "mean" plus `pna_weight`; one
+    graph at a time (ValueError with `batch` or live_edge_weight)."""
     def __init__(self, in_channels: int, out_channels: int, activation=nn.ReLU(inplace=True), aggr="mean",
                  z_ratio=0.8, dropout=0.2, softmax_t=1.0, gat_slope=0.2, gat_heads=1, live_edge_weight=False, moment_eps=1e-5):
         super().__init__()
@@ -225,6 +241,8 @@ class GLASSConv(nn.Module):
         if aggr == "softmax":  # (no other configuration owns the key: their state_dict is unchanged)
             self.t = nn.Parameter(torch.full((1, ), self.softmax_t))
         self.moment_eps = float(moment_eps)
+        if aggr == "pna":  # (likewise: only this configuration owns the key)
+            self.pna_weight = nn.Parameter(torch.full((12, out_channels), 1.0 / 12.0))
         self.gat_slope = float(gat_slope)
         self.gat_heads = gat_heads
         if aggr == "gat":  # (likewise: only this configuration owns the two keys)
@@ -243,6 +261,7 @@ class GLASSConv(nn.Module):
         self.gn.reset_parameters()
         _reset_softmax_t(self)
         _reset_gat_att(self)
+        _reset_pna_weight(self)
 
     def forward(self, x_, edge_index, edge_weight, mask, out=None, batch=None):
         """`out` (optional, fused path only): a preallocated [N,H] view (a slice of the JK buffer) to write into.
@@ -251,7 +270,7 @@ class GLASSConv(nn.Module):
         calls key only on the row's label byte and take the R * N rows as they are."""
         if self.live_edge_weight and batch is not None:
             raise ValueError("GLASSConv: live_edge_weight has no replicated form (exact zero-one labels: `batch` given)")
-        if self.aggr in ("std", "var") and batch is not None:
+        if self.aggr in ("std", "var", "pna") and batch is not None:
             raise ValueError(f"GLASSConv: aggr {self.aggr!r} has no replicated form (exact zero-one labels: `batch` given)")
         if self.adj is None:
             self.adj = buildAdj(edge_index, edge_weight.detach() if self.live_edge_weight else edge_weight,
@@ -268,6 +287,9 @@ class GLASSConv(nn.Module):
             agg = lambda m: ops.spmm_gat(self.adj, m, self.att_src, self.att_dst, self.gat_slope, self.gat_heads)
         elif self.aggr in ("std", "var"):
             agg = lambda m: ops.spmm_moments(self.adj, m, self.aggr, self.moment_eps)[0]
+        elif self.aggr == "pna":
+            agg = lambda m: ops.pna_mix(*ops.spmm_pna(self.adj, m, self.moment_eps), self.adj.pna_wsum, self.adj.pna_delta,
+                                        self.pna_weight)
         else:
             agg = lambda m: ops.spmm(self.adj, m)
         rep = {} if batch is None else {"rep": batch}  # (a training pass collects the weight gradients replica by replica)

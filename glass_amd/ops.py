@@ -267,6 +267,80 @@ def spmm_moments(adj, x, kind="std", eps=1e-5):
     return SpMMMomentFn.apply(adj, x, kind, float(eps))
 
 
+class SpMMPnaFn(torch.autograd.Function):
+    """(mu, mx, mn, s) = the weighted mean, the largest and the smallest, and the weighted standard deviation of the messages
+    x[col] over the entries of row i of A (aggr "pna", K1p: csrc/spmm_pna.hip), from one gather of every source row.  The node
+    keeps x, mu, s, the winning entries of both extremes and the rows' weight sums; the backward is one transposed pass for all
+    four results (A carries no gradient)."""
+    @staticmethod
+    def forward(ctx, adj, x, eps):
+        _need_gpu(x)
+        x, _ = _rows(x)
+        mu, s, mx, mn, amx, amn, wsum = adj.pna_fwd(x, eps)
+        ctx.adj = adj
+        ctx.save_for_backward(x, mu, s, amx, amn, wsum)
+        ctx.set_materialize_grads(False)  # a result nobody used arrives as None, not as zeros
+        return mu, mx, mn, s
+
+    @staticmethod
+    def backward(ctx, dmu, dmx, dmn, ds):
+        if not ctx.needs_input_grad[1] or (dmu is None and dmx is None and dmn is None and ds is None):
+            return None, None, None
+        x, mu, s, amx, amn, wsum = ctx.saved_tensors
+        A, C = pna_factors(s, wsum, ds, dmu)
+        zero = None
+        rows = []
+        for g in (dmx, dmn):  # the kernel has one form: a result without a gradient hands it zeros
+            if g is None:
+                g = zero = torch.zeros_like(s) if zero is None else zero
+            else:
+                g, _ = _rows(g)
+            rows.append(g)
+        return None, ctx.adj.pna_bwd(x, mu, A, C, amx, rows[0], amn, rows[1]), None
+
+
+def pna_factors(s, wsum, ds, dmu):
+    """(A, C) of K1p's backward from the forward's results and the gradients of S and Mu (either may be None: zeros) — per
+    destination, N * H work: A = dS / (W S), C = dMu / W; a row without entries gives 0."""
+    w = wsum[:, None]
+    live = w > 0
+    one = torch.ones((), dtype=s.dtype, device=s.device)
+    out = []
+    for g, den in ((ds, w * s), (dmu, w.expand_as(s))):
+        if g is None:
+            out.append(torch.zeros_like(s))
+        else:
+            g, _ = _rows(g)
+            out.append(torch.where(live, g / torch.where(live, den, one), torch.zeros_like(g)).contiguous())
+    return out[0], out[1]
+
+
+def spmm_pna(adj, x, eps=1e-5):
+    """PNA's four aggregators from one pass: `adj` a graph.CSRAdj built for aggr "pna".  Returns (Mu, Mx, Mn, S): per destination
+    and channel the weighted mean, the largest and the smallest neighbour message, and the weighted standard deviation
+    sqrt(Var + eps); zeros for a node without in-edges.  Differentiable in x through all four; under no_grad, when x needs no
+    gradient, or when no result received one, nothing of the backward is launched."""
+    if getattr(adj, "aggr", None) != "pna":
+        raise GlassHipError(f"spmm_pna: the adjacency was built for aggr {getattr(adj, 'aggr', None)!r}, not 'pna'")
+    return SpMMPnaFn.apply(adj, x, float(eps))
+
+
+def pna_mix(mu, mx, mn, s, wsum, delta, theta):
+    """PNA's degree scalers and a per-channel choice among the twelve views, plain differentiable torch:
+    Y[i, c] = sum over aggregators a (mean, max, min, std) and scalers k of s_k(i) * theta[3 a + k, c] * Agg_a[i, c] with
+    s_0 = 1, s_1 = log(W_i + 1) / delta (amplification), s_2 = delta / log(W_i + 1) (attenuation); wsum [N] the rows' weight
+    sums, delta a float (graph.CSRAdj.pna_delta), theta [12, H].  A row with W = 0 gives 0."""
+    live = wsum > 0
+    lw = torch.log1p(torch.where(live, wsum, torch.ones_like(wsum)))
+    zero = torch.zeros_like(wsum)
+    scal = (live.to(mu.dtype)[:, None], torch.where(live, lw / delta, zero)[:, None], torch.where(live, delta / lw, zero)[:, None])
+    y = None
+    for a, agg in enumerate((mu, mx, mn, s)):
+        coef = scal[0] * theta[3 * a] + scal[1] * theta[3 * a + 1] + scal[2] * theta[3 * a + 2]
+        y = agg * coef if y is None else y + agg * coef
+    return y
+
+
 def _heads_kw(heads):
     """heads == 1 calls the CSRAdj methods exactly as before the argument existed"""
     return {} if heads == 1 else {"heads": heads}
@@ -381,6 +455,8 @@ def spmm(adj, x):
                             "ops.spmm_gat(adj, x, att_src, att_dst, slope)")
     if getattr(adj, "aggr", None) in ("std", "var"):
         raise GlassHipError(f"spmm: a {adj.aggr} adjacency is no product; call ops.spmm_moments(adj, x, kind, eps)")
+    if getattr(adj, "aggr", None) == "pna":
+        raise GlassHipError("spmm: a pna adjacency is no product; call ops.spmm_pna(adj, x, eps)")
     return SpMMFn.apply(adj, x)
 
 
@@ -1201,7 +1277,7 @@ def spmm_rep(adj, x, R):
     if getattr(adj, "aggr", None) == "gat":
         raise GlassHipError("replicated gat aggregation is not built: aggr 'gat' runs one graph at a time (no exact "
                             "zero-one labels / --use_zeroone with it)")
-    if getattr(adj, "aggr", None) in ("std", "var"):
+    if getattr(adj, "aggr", None) in ("std", "var", "pna"):
         raise GlassHipError(f"replicated {adj.aggr} aggregation is not built: aggr '{adj.aggr}' runs one graph at a time (no exact "
                             "zero-one labels / --use_zeroone with it)")
     return SpMMRepFn.apply(adj, x, int(R))

@@ -224,6 +224,55 @@ int glass_spmm_moment_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, con
                               int64_t n_rows, int64_t H,
                               const int32_t* plan_t_header_host, const int32_t* plan_t_dev, void* ws, void* stream);
 
+/* K1p PNA neighbour aggregation (aggr "pna": an extension, the reference has none; Principal Neighbourhood Aggregation) at the
+ *     call site K1 serves, on K1's CSR and plans: mean, standard deviation, max and min of the neighbour messages from one
+ *     gather of every source row.  Forward CSR as for K1v (raw weights > 0 as multiplicities; the caller's check).
+ *
+ *   glass_spmm_pna_csr_f32: over the entries e of row i, x_e = X[col[e],c], w_e = val[e]:
+ *         W = sum_e w_e     Mu = sum_e w_e x_e / W     Var = sum_e w_e (x_e - Mu)^2 / W     S = sqrt(Var + eps)
+ *         Mx = max_e x_e    amx = the winning e        Mn = min_e x_e                       amn = the winning e
+ *     The extremes are over the raw message (a multiplicity does not move them; no product, no rounding: bit-for-bit
+ *     functions of the inputs); equal values (-0.0 == +0.0) go to the smaller e and the stored value is the winner's own bits.
+ *     A row without entries: Wsum = Mu = S = Mx = Mn = 0, amx = amn = -1.  The state per lane is the triple (W, mean, M2) of
+ *     K1v, merged by the same form of Chan's update (no x^2 is formed: equal messages give S == sqrt(eps) exactly), beside a
+ *     (best, arg) pair for each extreme; entries, lane groups, the four waves of a long-row item and the chunks of a cut row
+ *     merge in a fixed order: bitwise repeatable for a given plan.  ws: glass_spmm_pna_ws_bytes(hdr, H) = the plan's partial
+ *     slots times (6 H + 1) words; cut rows are merged by a second launch in slot order.
+ *   glass_spmm_pna_bwd_f32: on the TRANSPOSED CSR (row j = source, col_t = destinations i, val_t, eid_t[t] = the index of
+ *     transposed entry t in the forward CSR, its own plan):
+ *         dX[j,c] = sum over the entries t of row j of  val_t * (C[i,c] + A[i,c] * (X[j,c] - Mu[i,c]))
+ *                                                       + (amx[i,c] == eid_t ? Gmx[i,c] : 0) + (amn[i,c] == eid_t ? Gmn[i,c] : 0)
+ *     with A = dS / (Wsum S), C = dMu / Wsum, Gmx = dMx, Gmn = dMn [n, H] from the caller (0 where Wsum = 0).  All four are
+ *     required: a result without a gradient is a buffer of zeros.  X - Mu is formed per entry, never factored out of the sum;
+ *     fixed order, no float atomics, bitwise repeatable.  Row j's own X row is read once; per entry seven [H] rows of the
+ *     destination.  ws: glass_spmm_pna_bwd_ws_bytes(hdr_t, H) = the plan's partial slots times H floats.
+ *   Both: every H and leading dimension K1v takes (16-byte vector form when H, the ld* and the pointers allow it, scalar form
+ *     otherwise).  Refused on the host before any launch: null or misaligned pointers, H <= 0, ld* < H, eps < 0, partial slots
+ *     without ws -> GLASS_E_ARG; a header that is no plan for n_rows -> GLASS_E_PLAN; H beyond 65535 * 64 columns ->
+ *     GLASS_E_UNSUPPORTED.  n_rows == 0 returns 0 without a launch.  The *_ws_bytes queries: GLASS_E_PLAN for a header that
+ *     is no plan, GLASS_E_ARG for H <= 0. */
+int64_t glass_spmm_pna_ws_bytes(const int32_t* plan_header_host, int64_t H);
+int glass_spmm_pna_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val, /* CSR of A, device */
+                           const float* X, int64_t ldx,                                 /* [n_cols, H] */
+                           float eps,
+                           float* Mu, int64_t ldmu, float* S, int64_t lds,              /* [n_rows, H] each */
+                           float* Mx, int64_t ldmx, float* Mn, int64_t ldmn,            /* likewise */
+                           int32_t* amx, int64_t ldamx, int32_t* amn, int64_t ldamn,    /* likewise, int32 */
+                           float* Wsum,                                                 /* [n_rows] */
+                           int64_t n_rows, int64_t H,
+                           const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_spmm_pna_bwd_ws_bytes(const int32_t* plan_t_header_host, int64_t H);
+int glass_spmm_pna_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* val_t,   /* CSR of A^T */
+                           const int32_t* eid_t,                                                /* [nnz] */
+                           const float* X, int64_t ldx,                                         /* [n_rows, H] */
+                           const float* Mu, int64_t ldmu, const float* A, int64_t lda,          /* [n_cols of A^T, H] each */
+                           const float* C, int64_t ldc,                                         /* likewise */
+                           const int32_t* amx, int64_t ldamx, const float* Gmx, int64_t ldgmx,  /* likewise */
+                           const int32_t* amn, int64_t ldamn, const float* Gmn, int64_t ldgmn,  /* likewise */
+                           float* dX, int64_t lddx,                                             /* [n_rows, H] */
+                           int64_t n_rows, int64_t H,
+                           const int32_t* plan_t_header_host, const int32_t* plan_t_dev, void* ws, void* stream);
+
 /* K1a attention neighbour aggregation (aggr "gat": an extension, the reference has none; single-head GAT) at the call site K1
  *     serves, on K1's CSR and plans.  Forward CSR as for K1s (raw weights > 0, multiplicities; the caller's check).  att_src,
  *     att_dst: two [H] fp32 vectors in device memory; slope: LeakyReLU's negative slope, by value.  With
