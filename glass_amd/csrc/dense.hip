@@ -318,11 +318,11 @@ __global__ __launch_bounds__(kWave * RW * CS) void dual_fwd_kernel(const float* 
         });
     D_STAMP(2, 2);
     // epilogue: acc[4gl+k][reg] is row row0 + 4q + reg, column 64g + 4i + k (g = NGL*cg + gl) -> float4 per (row, group)
-    float ssum[NGL][4], ssq[NGL][4];  // this lane's column sums over its (up to) 4 rows, for the GraphNorm that follows
+    double ssum[NGL][4], ssq[NGL][4];  // this lane's column sums over its (up to) 4 rows, for the GraphNorm that follows
 #pragma unroll
     for (int g = 0; g < NGL; ++g)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) ssum[g][k] = ssq[g][k] = 0.f;
+        for (int k = 0; k < 4; ++k) ssum[g][k] = ssq[g][k] = 0.0;
     float4 bv[2 * NGL];
 #pragma unroll
     for (int gl = 0; gl < NGL; ++gl) {
@@ -355,8 +355,8 @@ __global__ __launch_bounds__(kWave * RW * CS) void dual_fwd_kernel(const float* 
                 float a1 = v1[k], a0 = v0[k];
                 a1 = act_fast(act, a1), a0 = act_fast(act, a0);
                 o[k] = w1 * a1 + w0 * a0;
-                ssum[gl][k] += o[k];
-                ssq[gl][k] = fmaf(o[k], o[k], ssq[gl][k]);
+                ssum[gl][k] += (double)o[k];
+                ssq[gl][k] += (double)o[k] * (double)o[k];
             }
             *reinterpret_cast<float4*>(out + r * ldo + c) = make_float4(o[0], o[1], o[2], o[3]);
         }
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(kWave * RW * CS) void dual_fwd_kernel(const float* 
     for (int gl = 0; gl < NGL; ++gl)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            double s = (double)ssum[gl][k], q2 = (double)ssq[gl][k];
+            double s = ssum[gl][k], q2 = ssq[gl][k];
             s += __shfl_xor(s, 16);
             q2 += __shfl_xor(q2, 16);
             s += __shfl_xor(s, 32);
@@ -1377,7 +1377,7 @@ __global__ __launch_bounds__(4 * H * WG) void comb_fwd_eff2_kernel(const float* 
             *reinterpret_cast<float4*>(T + rs * RS + H + 4 * ga) = hraw;
         }
     };
-    float ssum = 0.f, ssq = 0.f;  // this lane's column 16w + j over the rows 4q + r of every stage
+    double ssum = 0.0, ssq = 0.0;  // this lane's column 16w + j over the rows 4q + r of every stage (fp64: the exact accumulators get exact partials)
     commit(0, prep(0, rawA[0]), rawA[1]);
     if (2 < NSTG) issue(2, rawA);
     lds_barrier();
@@ -1444,8 +1444,8 @@ __global__ __launch_bounds__(4 * H * WG) void comb_fwd_eff2_kernel(const float* 
             const bool live = rv[r] >= 0 && !(rv[r] >> 30);
             const float o = acc0[r] + acc1[r] + be;
             buf_store1(r_out, live ? (int)((rv[r] * ldo + 16 * w + j) * 4) : kBufOOB, o);
-            ssum += live ? o : 0.f;
-            ssq += live ? o * o : 0.f;
+            ssum += live ? (double)o : 0.0;
+            ssq += live ? (double)o * (double)o : 0.0;
         }
 #if GLASS_STAGE_INTERLEAVE
         // one MFMA, then a few of the next stage's VALU instructions, 32 times
@@ -1461,7 +1461,7 @@ __global__ __launch_bounds__(4 * H * WG) void comb_fwd_eff2_kernel(const float* 
     }
     D_STAMP(1, 3);
     if (stats == nullptr) return;
-    double s = (double)ssum, q2 = (double)ssq;
+    double s = ssum, q2 = ssq;
     s += __shfl_xor(s, 16);
     q2 += __shfl_xor(q2, 16);
     s += __shfl_xor(s, 32);
@@ -1642,7 +1642,7 @@ __global__ __launch_bounds__(4 * H * WG) void comb_fwd_eff3_kernel(const float* 
         }
         if (ga == 0) rowflag_s[st & 1][rs] = (r >= 0 && R.mk != 0) ? (r | (1 << 30)) : r;  // labeled row of a main tile: an extra workgroup stores it
     };
-    float ssum = 0.f, ssq = 0.f;
+    double ssum = 0.0, ssq = 0.0;  // (fp64: the exact accumulators get exact partials)
     commit(0, rawA);
     issue(2, rawA);
     lds_barrier();
@@ -1698,8 +1698,8 @@ __global__ __launch_bounds__(4 * H * WG) void comb_fwd_eff3_kernel(const float* 
             const bool live = rv[r] >= 0 && !(rv[r] >> 30);
             const float o = acc0[r] + acc1[r] + be;
             buf_store1(r_out, live ? (int)((rv[r] * ldo + 16 * w + j) * 4) : kBufOOB, o);
-            ssum += live ? o : 0.f;
-            ssq += live ? o * o : 0.f;
+            ssum += live ? (double)o : 0.0;
+            ssq += live ? (double)o * (double)o : 0.0;
         }
         if (st + 1 < nst) lds_barrier();
     };
@@ -1708,7 +1708,7 @@ __global__ __launch_bounds__(4 * H * WG) void comb_fwd_eff3_kernel(const float* 
         if (st + 1 < nst) stage(st + 1, rawA);
     }
     if (stats == nullptr) return;
-    double s = (double)ssum, q2 = (double)ssq;
+    double s = ssum, q2 = ssq;
     s += __shfl_xor(s, 16);
     q2 += __shfl_xor(q2, 16);
     s += __shfl_xor(s, 32);
@@ -1868,7 +1868,7 @@ __global__ __launch_bounds__(kBlock * WG) void trans_fwd2_kernel(const float* __
             *reinterpret_cast<float4*>(tile[SP ? 0 : (st & 1)] + rs * RS + 4 * ga) = v;
         }
     };
-    float ssum = 0.f, ssq = 0.f;
+    double ssum = 0.0, ssq = 0.0;  // (fp64: the exact accumulators get exact partials)
     stage_store(0, rawA);
     if (2 < NSTG) rawA = issue(2);
     lds_barrier();
@@ -1942,14 +1942,14 @@ __global__ __launch_bounds__(kBlock * WG) void trans_fwd2_kernel(const float* __
             a1 = act_fast(act, a1), a0 = act_fast(act, a0);
             const float o = w1 * a1 + w0 * a0;
             buf_store1(r_out, live ? (int)((row * ldo + c) * 4) : kBufOOB, o);
-            ssum += live ? o : 0.f;
-            ssq += live ? o * o : 0.f;
+            ssum += live ? (double)o : 0.0;
+            ssq += live ? (double)o * (double)o : 0.0;
         }
         if (st + 1 < NSTG) lds_barrier();
     }
     D_STAMP(2, 3);
     if (stats == nullptr) return;
-    double s = (double)ssum, q2 = (double)ssq;
+    double s = ssum, q2 = ssq;
     s += __shfl_xor(s, 16);
     q2 += __shfl_xor(q2, 16);
     s += __shfl_xor(s, 32);

@@ -124,3 +124,34 @@ PYTHON_SWITCHES = [
 # switch of PYTHON_SWITCHES outside glass_amd.train, GLASS_GN_EXACT_FWD, and GLASS_DENSE_H128 / GLASS_DENSE_H256 (ops._DENSE_OFF)
 STEP_SWITCHES = [s for s in PYTHON_SWITCHES if s[0] != "glass_amd.train"] + [
     ("glass_amd.stack", "USE_GN_EXACT_FWD", False), ("glass_amd.ops", "_DENSE_OFF", {128}), ("glass_amd.ops", "_DENSE_OFF", {256})]
+
+
+class Buf:
+    """a [rows, cols] fp32 / fp64 view with leading dimension ld = cols + 4, two guard rows in front and behind, in a NaN-filled flat
+    buffer; 16-byte aligned.  tail: what the two guard rows behind hold (inputs: Inf, NaN)."""
+    def __init__(self, rows, cols, src=None, dtype=torch.float32, tail=None, pad=4):
+        ld = cols + pad   # (pad = 0: the contiguous [tile][2][H] partials, guarded by the rows in front and behind)
+        self.ld, self.rows, self.cols = ld, rows, cols
+        self.flat = torch.full(((rows + 4) * ld + 8, ), float("nan"), dtype=dtype, device="cuda:0")
+        off = 2 * ld + 4
+        self.v = torch.as_strided(self.flat, (rows, cols), (ld, 1), off)
+        assert self.v.data_ptr() % 16 == 0
+        if src is not None:
+            self.v.copy_(torch.as_tensor(src))
+        if tail is not None:
+            torch.as_strided(self.flat, (1, cols), (ld, 1), off + rows * ld).fill_(tail)
+        self.inside = torch.zeros(self.flat.numel(), dtype=torch.bool, device="cuda:0")
+        torch.as_strided(self.inside, (rows, cols), (ld, 1), off).fill_(True)
+
+    @property
+    def ptr(self):
+        return self.v.data_ptr()
+
+    def check(self, tag, allow_nan=False):
+        assert bool(torch.isnan(self.flat[~self.inside]).all()), f"{tag}: written outside its view (guard rows / columns)"
+        if not allow_nan:
+            assert not bool(torch.isnan(self.flat[self.inside]).any()), f"{tag}: NaN or unwritten element inside its view"
+        return self
+
+    def cpu(self):
+        return self.v.detach().cpu()

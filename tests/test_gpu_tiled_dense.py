@@ -7,7 +7,7 @@ hold Inf / NaN (what lies behind row N - 1 reaches nothing); every case runs twi
 it was written for through the restated dispatch.  The product form is the call's option in the act word.
 
 Out of scope (tiled_dense_oracle.reaches_tiled): the hidden-128 trans forward and both hidden-128 data gradients (stage-run kernels
-of dense.hip), the K5t weight gradients.
+of dense.hip: tests/test_gpu_staged_dense.py), the K5t weight gradients.
 
 One case fails on the parent commit's library: tests/test_tiled_dense_host.py::test_k5t_entry_codes_on_the_host_before_any_launch
 (the data gradient took any act code).
@@ -25,6 +25,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import graphnorm_oracle as G  # noqa: E402
 import tiled_dense_oracle as TD  # noqa: E402
+from helpers import Buf  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -63,37 +64,6 @@ def _ok(rc):
 
 def _act_word(act, f32p):
     return int(act) | (_f32_bit() if f32p else 0)
-
-
-class Buf:
-    """a [rows, cols] fp32 / fp64 view with leading dimension ld = cols + 4, two guard rows in front and behind, in a NaN-filled flat
-    buffer; 16-byte aligned.  tail: what the two guard rows behind hold (inputs: Inf, NaN)."""
-    def __init__(self, rows, cols, src=None, dtype=torch.float32, tail=None, pad=4):
-        ld = cols + pad   # (pad = 0: the contiguous [tile][2][H] partials, guarded by the rows in front and behind)
-        self.ld, self.rows, self.cols = ld, rows, cols
-        self.flat = torch.full(((rows + 4) * ld + 8, ), NAN, dtype=dtype, device=DEV)
-        off = 2 * ld + 4
-        self.v = torch.as_strided(self.flat, (rows, cols), (ld, 1), off)
-        assert self.v.data_ptr() % 16 == 0
-        if src is not None:
-            self.v.copy_(torch.as_tensor(src))
-        if tail is not None:
-            torch.as_strided(self.flat, (1, cols), (ld, 1), off + rows * ld).fill_(tail)
-        self.inside = torch.zeros(self.flat.numel(), dtype=torch.bool, device=DEV)
-        torch.as_strided(self.inside, (rows, cols), (ld, 1), off).fill_(True)
-
-    @property
-    def ptr(self):
-        return self.v.data_ptr()
-
-    def check(self, tag, allow_nan=False):
-        assert bool(torch.isnan(self.flat[~self.inside]).all()), f"{tag}: written outside its view (guard rows / columns)"
-        if not allow_nan:
-            assert not bool(torch.isnan(self.flat[self.inside]).any()), f"{tag}: NaN or unwritten element inside its view"
-        return self
-
-    def cpu(self):
-        return self.v.detach().cpu()
 
 
 def _vec(src, dtype=torch.float32):

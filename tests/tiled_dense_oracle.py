@@ -5,8 +5,8 @@ tests/test_tiled_dense_host.py) and fp32 restatements of the kernels' summation 
 
 Scope.  The family serves, in the default build: the forward of the comb pair at hidden 128 and of both pairs at hidden 256 / 512,
 and the data gradient of both pairs at hidden 256 / 512.  The hidden-128 trans forward and both hidden-128 data gradients left it
-for the stage-run kernels of dense.hip (trans_fwd3 / trans_dgrad2 / trans_dgrad3 / comb_dgrad3): OUT OF SCOPE here, not tested by
-these files (`reaches_tiled` says so and the host test ties it to the entry's text).  The K5t weight gradients are not part of it.
+for the stage-run kernels of dense.hip (trans_fwd3 / trans_dgrad2 / trans_dgrad3 / comb_dgrad3): OUT OF SCOPE here — they are tested by
+tests/staged_dense_oracle.py and tests/test_gpu_staged_dense.py — (`reaches_tiled` says so and the host test ties it to the entry's text).  The K5t weight gradients are not part of it.
 
 Stages (every function -> (want, mass), fp64; each a function of what the kernel really read — its own upstream outputs as read
 back where a stage consumes them —, so that one stage's rounding is left to bound; the pattern of tests/graphnorm_oracle.py, whose

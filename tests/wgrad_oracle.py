@@ -9,7 +9,7 @@ three instantiations, wgrad128_trans_kernel, wgrad128_comb_kernel with its list 
 tiled_wgrad8_kernel<EFF> plus the four-wave labeled-rows launch, and the reduce launch behind each of them.
 
 OUT OF SCOPE, not tested by these files: hidden <= 32 (dense_narrow.hip: tests of its own); the hidden-64 fused backward launches of
-dense.hip and their S / L partials (glass_dual_linear_bwd_f32, glass_comb_eff_bwd_f32); glass_linear_wgrad_reduce_batch_f32 and
+dense.hip and their S / L partials (glass_dual_linear_bwd_f32, glass_comb_eff_bwd_f32: tests/staged_dense_oracle.py, tests/test_gpu_staged_dense.py); glass_linear_wgrad_reduce_batch_f32 and
 glass_wgrad_reduce_spmm_f32 beyond the deferred-reduce cases of tests/test_gpu_wgrad.py (tests/test_gpu_step_tail.py has them); the
 non-eff fallback at rows_per_slab > 2 * kTile - 64, which needs more than 2 M rows.
 
