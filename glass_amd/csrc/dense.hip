@@ -68,6 +68,14 @@ namespace glass {
 #ifdef GLASS_DENSE_TRACE
 __device__ unsigned long long* g_dense_trace;
 __device__ int g_dense_trace_sel;
+// sel 6: the prologue workgroups of the step's head launch, [row * gridDim.x + workgroup][wave][slot] (tools/head_trace.py)
+#define HEAD_STAMP(slot)                                                                                                   \
+    do {                                                                                                                   \
+        if (g_dense_trace && g_dense_trace_sel == 6 && (threadIdx.x & 63) == 0 && threadIdx.x < 256)                       \
+            g_dense_trace[((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)) * 8 + (slot)] = wall_clock64(); \
+    } while (0)
+#else
+#define HEAD_STAMP(slot) do { } while (0)
 #endif
 
 
@@ -3116,17 +3124,29 @@ __global__ __launch_bounds__(kLabThreads) void step_head_kernel(PackBatch batch,
                                                                 ZeroJob zero, int rows, LabelJob lj) {
     if ((int)blockIdx.y < rows) {
         if (threadIdx.x >= kBlock) return;
+        HEAD_STAMP(0);
         pack_batch_body(batch, rng_state, tab, n_jobs, zero, rows);
+        HEAD_STAMP(4);
         return;
     }
     if (blockIdx.x != 0) return;
+    D_STAMP(5, 0);
     // (wave-uniform scalar loads: one dependent round trip in front of the body's own)
     const int64_t n_b = lj.cur->n_batches, c = lj.cur->cursor;
     const int64_t b = c < 0 ? 0 : (lj.cur->wrap ? c % n_b : (c >= n_b ? n_b - 1 : c));
     const BatchSrc src{lj.cur->pos_all, reinterpret_cast<const uint32_t*>(lj.cur->y_all), lj.cur->idx + b * lj.n_idx, lj.smax,
                        lj.y_row_words > 0 ? lj.y_row_words : 1, lj.cur->n_all};
-    batch_labels_body<true>(src, lj.n_idx * lj.smax, lj.pos_dst, lj.y_dst, (int64_t)lj.n_idx * lj.y_row_words, lj.mask, lj.lab_rows,
-                            lj.lab_count, lj.owner, lj.N, 1);
+    // the epoch's plan (glass_epoch_plan_build; the same scalar round trip as the cursor): the batch's unique labeled rows
+    // are copied from its record; NULL: elected here, step by step
+    const int32_t* plan = lj.cur->plan;
+    D_STAMP(5, 1);
+    if (plan)
+        batch_labels_plan_body<true>(src, lj.n_idx * lj.smax, lj.pos_dst, lj.y_dst, (int64_t)lj.n_idx * lj.y_row_words, lj.mask,
+                                     lj.lab_rows, lj.lab_count, plan + b * epoch_plan_stride((int64_t)lj.n_idx * lj.smax), lj.N);
+    else
+        batch_labels_body<true>(src, lj.n_idx * lj.smax, lj.pos_dst, lj.y_dst, (int64_t)lj.n_idx * lj.y_row_words, lj.mask,
+                                lj.lab_rows, lj.lab_count, lj.owner, lj.N, 1);
+    D_STAMP(5, 4);
     if (threadIdx.x == 0) lj.cur->cursor = c + 1;  // (every read of the cursor lies before the body's barriers)
 }
 

@@ -57,3 +57,41 @@ extern "C" int glass_batch_labels_gather(const int64_t* pos_all, int64_t n_all, 
                        incremental);
     return launch_status("glass_batch_labels_gather");
 }
+
+// ---- the epoch plan: the unique labeled rows of EVERY batch of an epoch, once (labels_body.h) --------------------------
+// One workgroup per lane of owner words; lane g takes batches g, g + lanes, ... of the epoch, one after the other.
+namespace glass {
+__global__ __launch_bounds__(kLabThreads) void epoch_plan_kernel(const int64_t* __restrict__ pos_all, int64_t n_all, int smax,
+                                                                 const int64_t* __restrict__ idx, int n_batches, int n_idx,
+                                                                 int32_t* __restrict__ plan, int32_t* __restrict__ owner,
+                                                                 int64_t N) {
+    const int n_pos = n_idx * smax;
+    const int64_t stride = epoch_plan_stride(n_pos);
+    for (int b = blockIdx.x; b < n_batches; b += gridDim.x) {
+        const BatchSrc src{pos_all, nullptr, idx + (int64_t)b * n_idx, smax, 1, n_all};
+        int32_t* rec = plan + b * stride;
+        unique_rows_body<true>(src, n_pos, rec + kPlanHead, rec, owner + (int64_t)blockIdx.x * N, N);
+    }
+}
+}  // namespace glass
+
+extern "C" int64_t glass_epoch_plan_bytes(int64_t n_batches, int64_t n_idx, int64_t smax) {
+    if (n_batches <= 0 || n_idx <= 0 || smax <= 0 || n_idx * smax >= (1ll << 30) || n_batches >= (1ll << 31)) return GLASS_E_ARG;
+    return n_batches * epoch_plan_stride(n_idx * smax) * (int64_t)sizeof(int32_t);
+}
+
+extern "C" int glass_epoch_plan_build(const int64_t* pos_all, int64_t n_all, int64_t smax, const int64_t* idx,
+                                      int64_t n_batches, int64_t n_idx, int64_t n_nodes, int32_t* plan, int64_t plan_bytes,
+                                      void* ws, int64_t ws_lanes, void* stream) {
+    GLASS_REQUIRE(pos_all && idx && plan && ws, "epoch_plan_build: null pointer");
+    GLASS_REQUIRE(n_all > 0 && smax > 0 && n_idx > 0 && n_idx * smax < (1ll << 30) && smax < (1ll << 30) && n_batches > 0 &&
+                      n_batches < (1ll << 31) && n_nodes > 0 && n_nodes < (1ll << 31) && ws_lanes > 0 && ws_lanes <= 1024,
+                  "epoch_plan_build: bad sizes");
+    GLASS_REQUIRE(plan_bytes >= glass_epoch_plan_bytes(n_batches, n_idx, smax) && (reinterpret_cast<uintptr_t>(plan) & 15u) == 0,
+                  "epoch_plan_build: the plan needs %lld bytes (glass_epoch_plan_bytes), 16-B aligned",
+                  (long long)glass_epoch_plan_bytes(n_batches, n_idx, smax));
+    const unsigned lanes = (unsigned)(ws_lanes < n_batches ? ws_lanes : n_batches);
+    hipLaunchKernelGGL(epoch_plan_kernel, dim3(lanes), dim3(kLabThreads), 0, (hipStream_t)stream, pos_all, n_all, (int)smax, idx,
+                       (int)n_batches, (int)n_idx, plan, (int32_t*)ws, n_nodes);
+    return launch_status("glass_epoch_plan_build");
+}

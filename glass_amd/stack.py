@@ -77,6 +77,10 @@ class prologue_done:
         _PROLOGUE_DONE = self.prev
 
 
+EPOCH_PLAN_MAX_BYTES = 64 << 20   # an epoch plan (+ its owner words) above this is not built: the per-step path stays
+EPOCH_PLAN_LANES = 64             # batches the plan launch works on side by side (one block of owner words each)
+
+
 class BatchLabels:
     """Label state of one subgraph batch on the device (glass_batch_labels; utils.MaxZOZ, reference impl/utils.py:32-45):
     the label bytes `mask` (maintained incrementally from batch to batch), the unique labeled rows `rows[:count]` in
@@ -93,11 +97,15 @@ class BatchLabels:
         self.cursor = None
         self._epoch = None
         self.in_head = False   # the step's head launch labels the batch (set by TrainStep while an epoch source is installed)
+        self._plan = self._plan_ws = None   # the epoch plan and its owner words (_build_plan), kept from epoch to epoch
+        self.plan_bytes = 0                 # bytes of the installed epoch's plan; 0: none (the head launch lists the rows itself)
 
-    def set_epoch(self, pos_all, y_all, idx_batches, pos_dst, y_dst, wrap=False):
+    def set_epoch(self, pos_all, y_all, idx_batches, pos_dst, y_dst, wrap=False, plan=False):
         """Install the epoch's batches for the in-graph label launch: idx_batches int64 [n_batches, n_idx] (device, contiguous:
         the rows of every batch, in step order), pos_all / y_all the data set's matrices; the cursor restarts at batch 0
-        (wrap: it cycles over the batches instead of stopping at the last one).  One small host-to-device copy per epoch; the step's graph reads everything through the cursor (fixed address)."""
+        (wrap: it cycles over the batches instead of stopping at the last one).  plan: the unique labeled rows of every batch
+        are listed here, once (_build_plan), and the head launch copies its batch's list; the caller must not edit pos_all /
+        idx_batches in place before the next set_epoch.  One small host-to-device copy per epoch; the step's graph reads everything through the cursor (fixed address)."""
         n_all, smax = pos_all.shape
         n_b, n_idx = idx_batches.shape
         if n_idx * smax != self.cap:
@@ -105,10 +113,34 @@ class BatchLabels:
         yrb = 0 if y_all is None else y_all.element_size() * (y_all.numel() // max(y_all.shape[0], 1))
         if self.cursor is None:
             self.cursor = torch.zeros(8, dtype=torch.int64, device=self.mask.device)
-        desc = torch.tensor([pos_all.data_ptr(), 0 if y_all is None else y_all.data_ptr(), idx_batches.data_ptr(), n_all, n_b, 0, 1 if wrap else 0, 0],
-                            dtype=torch.int64)
+        plan_ptr = self._build_plan(pos_all, idx_batches) if plan else 0
+        desc = torch.tensor([pos_all.data_ptr(), 0 if y_all is None else y_all.data_ptr(), idx_batches.data_ptr(), n_all, n_b, 0, 1 if wrap else 0,
+                             plan_ptr], dtype=torch.int64)
         self.cursor.copy_(desc)
         self._epoch = (pos_all, y_all, idx_batches, pos_dst, y_dst, int(n_idx), int(smax), int(yrb))
+
+    def _build_plan(self, pos_all, idx_batches):
+        """The epoch's plan (glass_epoch_plan_build: every batch's unique labeled rows, one launch per epoch) into a buffer that
+        is kept and rewritten in place while its size fits; its address travels in the cursor record (device memory), so a
+        captured head launch follows it.  Returns the address, or 0 (the head launch then lists the rows itself) when the plan
+        would exceed EPOCH_PLAN_MAX_BYTES."""
+        n_all, smax = pos_all.shape
+        n_b, n_idx = idx_batches.shape
+        lib = _lib.load()
+        need = int(lib.glass_epoch_plan_bytes(n_b, n_idx, smax))
+        lanes = max(1, min(n_b, EPOCH_PLAN_LANES, EPOCH_PLAN_MAX_BYTES // max(4 * self.n, 1)))
+        if need <= 0 or need + 4 * self.n * lanes > EPOCH_PLAN_MAX_BYTES:
+            self.plan_bytes = 0
+            return 0
+        if self._plan is None or self._plan.numel() * 4 < need:
+            self._plan = torch.zeros(need // 4, dtype=torch.int32, device=self.mask.device)
+        if self._plan_ws is None or self._plan_ws.numel() < self.n * lanes:
+            self._plan_ws = torch.full((self.n * lanes,), 2**31 - 1, dtype=torch.int32, device=self.mask.device)
+        rc = lib.glass_epoch_plan_build(pos_all.data_ptr(), n_all, smax, idx_batches.data_ptr(), n_b, n_idx, self.n,
+                                        self._plan.data_ptr(), self._plan.numel() * 4, self._plan_ws.data_ptr(), lanes, _stream())
+        _check(rc, "glass_epoch_plan_build")
+        self.plan_bytes = need
+        return self._plan.data_ptr()
 
     def rewind(self):
         """The cursor back to the epoch's first batch (device-side: a fill on the current stream, outside any capture)."""

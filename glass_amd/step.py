@@ -30,6 +30,7 @@ CAPTURE_COLLECTIVE = os.environ.get("GLASS_CAPTURE_COLLECTIVE", "1") != "0"  # t
 # the verdict agreed on by all ranks.  On a mismatch the process keeps running on the split form (graph + eager collective).
 VERIFY_CAPTURED_COLLECTIVE = os.environ.get("GLASS_VERIFY_CAPTURED_COLLECTIVE", "1") != "0"
 _VERIFY_TOL = 1e-5
+EPOCH_PLAN = os.environ.get("GLASS_EPOCH_PLAN", "1") != "0"  # 0: the head launch derives the batch's lists itself, every step
 # (Prefetching the label launch of step i + 1 on a side stream beside step i's graph — two label / batch buffer sets, the step
 # captured once per set — was measured in round 4 at ppi_bp-shape: 0.2688-0.2694 ms/step with it against 0.2448 without;
 # the cross-stream event in front of every replay costs ~25 us, three times what the hidden launch returns.  Not part of
@@ -77,6 +78,9 @@ class TrainStep:
         self.exchange_enabled = True    # bench.py: False = skip the collectives (timing of the exposed share; ranks diverge)
         self._head_sig = None           # batch shape / target row size baked into a capture whose head launch labels the batch
         self._recapture = False         # the label form (in the head launch / eager in front of the step) changed since the capture
+        # begin_epoch lists every batch's unique labeled rows once per epoch (stack.BatchLabels._build_plan) instead of the head
+        # launch electing them every step; the plan's address lives in device memory, so switching needs no new capture
+        self.epoch_plan = EPOCH_PLAN
 
     def _opt_hyper(self):
         """(hyper, clip) the optimizer would bake into a capture now: optim's hyper() cut into its four Adam values and
@@ -412,7 +416,7 @@ class TrainStep:
         if self._labels is None or shape != tuple(self._pos.shape) or y_all.dtype != self._y.dtype:
             return False
         was_head = self._labels.in_head
-        self._labels.set_epoch(pos_all, y_all, idx_batches, self._pos, self._y, wrap=wrap)
+        self._labels.set_epoch(pos_all, y_all, idx_batches, self._pos, self._y, wrap=wrap, plan=self.epoch_plan)
         self._labels.in_head = True
         sig = self._labels.head_signature()
         hyper, clip = self._opt_hyper()
@@ -423,7 +427,7 @@ class TrainStep:
                 self._warmup()   # (eager steps through the same head launch: they consume the first batches of the cursor)
             self._hyper, self._clip, self._wsig, self._head_sig, self._recapture = hyper, clip, wsig, sig, False
             self._capture()
-            self._labels.set_epoch(pos_all, y_all, idx_batches, self._pos, self._y, wrap=wrap)  # cursor back to batch 0
+            self._labels.set_epoch(pos_all, y_all, idx_batches, self._pos, self._y, wrap=wrap, plan=self.epoch_plan)  # cursor back to batch 0
         return True
 
     def next_step(self):

@@ -460,6 +460,19 @@ int glass_batch_labels_gather(const int64_t* pos_all, int64_t n_all, int64_t sma
                               int32_t* lab_rows, int32_t* lab_count, void* ws, int64_t n_nodes, int incremental,
                               void* stream);
 
+/*     The epoch plan: what the label launch derives from the batch's entries alone — lab_rows / lab_count — for EVERY batch of
+ *     an epoch, by one launch when the epoch's index batches are installed (the loaders draw one permutation per epoch,
+ *     impl/SubGDataset.py:92-96, so these lists are functions of the epoch's data, not of the step).  idx int64[n_batches,
+ *     n_idx] as in glass_batch_cursor.  plan receives one record of 4 + round_up(n_idx * smax, 4) int32 words per batch: word
+ *     0 the number of unique labeled rows, words 4.. the rows, in the order and form glass_batch_labels_gather lists them
+ *     (the same owner election and compaction).  glass_epoch_plan_bytes: bytes of the plan (GLASS_E_ARG for bad sizes).
+ *     ws = int32[ws_lanes, n_nodes] scratch, every word INT32_MAX before the first call and again after every call; ws_lanes
+ *     (1 .. 1024) batches are worked on side by side.  glass_step_head_f32 reads the plan through glass_batch_cursor.plan. */
+int64_t glass_epoch_plan_bytes(int64_t n_batches, int64_t n_idx, int64_t smax);
+int glass_epoch_plan_build(const int64_t* pos_all, int64_t n_all, int64_t smax, const int64_t* idx, int64_t n_batches,
+                           int64_t n_idx, int64_t n_nodes, int32_t* plan, int64_t plan_bytes, void* ws, int64_t ws_lanes,
+                           void* stream);
+
 /* K3+K4 fused label + embedding   replaces `mask=(z>0.5)` and `input_emb(x)`
  *     (impl/models.py:242-248):  out[n,:] = W[x[n],:],  mask[n] = label of node n.
  *     The label comes from `z` (int64[N], as MaxZOZ produced it) when z != NULL, else from
@@ -984,6 +997,8 @@ typedef struct glass_batch_cursor {
     int64_t n_batches;
     int64_t cursor;         /* next batch; advanced by the launch */
     int64_t wrap;           /* != 0: batch cursor % n_batches (a loop over the same batches) instead of the clamp */
+    const int32_t* plan;    /* the epoch's plan (glass_epoch_plan_build over the SAME pos_all / idx / n_idx / smax / n_nodes), or
+                             * NULL: the launch elects the batch's unique labeled rows itself */
 } glass_batch_cursor;
 int glass_step_head_f32(const float* const* src, float* const* dst, const int64_t* dst_floats, const int64_t* NT,
                         const int64_t* KT, const int32_t* flags, const float* z_ratio, int64_t n_jobs, uint64_t* rng_state,
