@@ -70,7 +70,19 @@ def parse_args(argv=None):
                    help="(extension) after the last repeat write PATH (.npy, one fp32 per edge of the graph): the mean over the "
                         "test split's batches of |d loss / d edge_weight| of the trained model; aggregations mean, sum and gcn "
                         "only, not with --use_zeroone")
+    p.add_argument("--edge_dropout", type=float, default=None, metavar="P",
+                   help="(extension) edge dropout (DropEdge): every training step each layer drops a random share P in [0, 1) of "
+                        "the adjacency entries, drawn on the GPU, undirected edges as one (default: the config file's "
+                        "`edge_dropout`, else 0); aggregations mean, sum and gcn only, not with --use_zeroone or --edge_saliency")
     args = p.parse_args(argv)
+    if args.edge_dropout is not None and not (0.0 <= args.edge_dropout < 1.0):
+        p.error("--edge_dropout must lie in [0, 1)")
+    if args.edge_dropout and args.use_zeroone:
+        p.error("--edge_dropout is not available with --use_zeroone (no edge dropout on the replicated path)")
+    if args.edge_dropout and args.edge_saliency is not None:
+        p.error("--edge_dropout is not available with --edge_saliency (edge dropout and live edge weights exclude each other)")
+    if args.edge_dropout and args.aggr not in (None, "mean", "sum", "gcn"):
+        p.error(f"--edge_dropout needs --aggr mean, sum or gcn ({args.aggr} needs a dropped edge excluded, not weighted zero)")
     if args.edge_saliency is not None and args.use_zeroone:
         p.error("--edge_saliency is not available with --use_zeroone (no edge-weight gradient on the replicated path)")
     if args.edge_saliency is not None and args.aggr not in (None, "mean", "sum", "gcn"):
@@ -152,7 +164,7 @@ class Run:
                 SubGDataset.GDataloader(self.val, batch_size, shuffle=True, drop_last=False),
                 SubGDataset.GDataloader(self.tst, batch_size, shuffle=True, drop_last=False))
 
-    def build_model(self, hidden_dim, conv_layer, dropout, jk, pool, z_ratio, aggr, gat_heads=None):
+    def build_model(self, hidden_dim, conv_layer, dropout, jk, pool, z_ratio, aggr, gat_heads=None, edge_dropout=0.0):
         a = self.args
         if pool not in POOLS:
             raise NotImplementedError
@@ -162,7 +174,8 @@ class Run:
                                     activation=nn.ELU(inplace=True), jk=jk, dropout=dropout,
                                     conv=functools.partial(models.GLASSConv, aggr=aggr, z_ratio=z_ratio, dropout=dropout,
                                                            gat_slope=getattr(a, "gat_slope", 0.2),
-                                                           gat_heads=getattr(a, "gat_heads", 1) if gat_heads is None else gat_heads),
+                                                           gat_heads=getattr(a, "gat_heads", 1) if gat_heads is None else gat_heads,
+                                                           edge_dropout=edge_dropout),
                                     gn=True)
             if a.use_nodeid:
                 print("load ", f"./Emb/{a.dataset}_{hidden_dim}.pt")
@@ -214,9 +227,12 @@ class Run:
         return epoch + 1, seconds, policy.best_val, policy.test_at_best
 
     def test(self, pool="size", aggr="mean", hidden_dim=64, conv_layer=8, dropout=0.3, jk=1, lr=1e-3, z_ratio=0.8,
-             batch_size=None, resi=0.7, gat_heads=None):
+             batch_size=None, resi=0.7, gat_heads=None, edge_dropout=None):
         """Train `repeat` times with one hyper-parameter set (the YAML keys); prints the reference's log lines.  gat_heads (an
-        extension key, aggr "gat" only): the attention heads; absent, --gat_heads."""
+        extension key, aggr "gat" only): the attention heads; absent, --gat_heads.  edge_dropout (an extension key, aggr "mean" /
+        "sum" / "gcn" only): the share of edges every layer drops per training step; absent, --edge_dropout, else 0."""
+        if edge_dropout is None:
+            edge_dropout = getattr(self.args, "edge_dropout", None) or 0.0
         # evaluation cadence: both the warm-up and the patience are 100 test-set batches' worth of epochs (synthetic
         # sets: a fifth of that)
         batches_in_test = self.tst.y.shape[0] / batch_size
@@ -228,7 +244,7 @@ class Run:
             set_seed((1 << repeat) - 1)
             print(f"repeat {repeat}")
             self.split()
-            model = self.build_model(hidden_dim, conv_layer, dropout, jk, pool, z_ratio, aggr, gat_heads)
+            model = self.build_model(hidden_dim, conv_layer, dropout, jk, pool, z_ratio, aggr, gat_heads, edge_dropout)
             optimizer = Adam(model.parameters(), lr=lr)  # (impl.train.train runs it as one fused launch inside the step's graph)
             if self.args.clip is not None:
                 # torch keeps unknown group keys; the step reads this one (norm launch + clipped Adam inside the step's graph)
@@ -301,6 +317,14 @@ def main(argv=None):
         params["aggr"] = args.aggr
     if args.gat_heads != 1:  # (the flag, where given, instead of the config file's `gat_heads`)
         params["gat_heads"] = args.gat_heads
+    if args.edge_dropout is not None:  # (the flag, where given, instead of the config file's `edge_dropout`)
+        params["edge_dropout"] = args.edge_dropout
+    if params.get("edge_dropout"):
+        if params.get("aggr", "mean") not in ("mean", "sum", "gcn"):
+            raise SystemExit(f"edge_dropout needs aggr mean, sum or gcn; the configuration says {params['aggr']!r} "
+                             "(the other aggregations need a dropped edge excluded, not weighted zero)")
+        if args.use_zeroone or args.edge_saliency is not None:
+            raise SystemExit("edge_dropout is not available with --use_zeroone or --edge_saliency")
     if args.edge_saliency is not None and params.get("aggr", "mean") not in ("mean", "sum", "gcn"):
         raise SystemExit(f"--edge_saliency needs aggr mean, sum or gcn; the configuration says {params['aggr']!r} "
                          "(no edge-weight gradient for the other aggregations)")

@@ -124,6 +124,7 @@ SIGNATURES = {
     "glass_adj_colsum_ws_bytes": (c_int64, [_P]),
     "glass_adj_colsum_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "glass_adj_values_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, c_int, _P, _P]),
+    "glass_adj_dropedge_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, c_int, c_float, c_int, _P, c_uint64, _P, _P, _P, _P, _P]),
     "glass_maxzoz_i64": (c_int, [_P, _I, _P, _I, _P]),
     "glass_embed_label_f32": (c_int, [_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _P]),
     "glass_mix_fwd_f32": (c_int, [_P, _I, _P, c_double, c_int, _P, _I, _I, _I, _P]),

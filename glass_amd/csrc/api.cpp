@@ -239,3 +239,28 @@ extern "C" int glass_adj_values_bwd_f32(const int32_t* rowptr, const int32_t* co
     if (nnz == 0) return 0;
     return glass::adj_values_bwd_launch(rowptr, col, perm, deg, dval, R, C, n_rows, nnz, aggr, dw, stream);
 }
+
+// ---- K2d  edge dropout (glass_adj_dropedge_f32): host-side validation, then the launches in spmm_dropedge.hip ---------------------
+namespace glass {
+int adj_dropedge_launch(const int32_t*, const int32_t*, const float*, const int32_t*, const int32_t*, const float*, int64_t, int,
+                        float, int, const int64_t*, uint64_t, float*, float*, float*, uint8_t*, void*);
+}  // namespace glass
+
+extern "C" int glass_adj_dropedge_f32(const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rowptr_t,
+                                      const int32_t* col_t, const float* w_t, int64_t n_rows, int aggr, float p, int symmetric,
+                                      const int64_t* rng, uint64_t call_id, float* deg, float* val, float* val_t, uint8_t* keep,
+                                      void* stream) {
+    if (aggr < 0 || aggr > 2) {
+        glass::set_error("adj_dropedge: unknown aggr %d (0=mean,1=sum,2=gcn)", aggr);
+        return GLASS_E_UNSUPPORTED;
+    }
+    SEG_REQUIRE(n_rows >= 0 && n_rows < INT32_MAX, "adj_dropedge: n_rows %lld outside [0, 2^31 - 1)", (long long)n_rows);
+    SEG_REQUIRE(p >= 0.f && p < 1.f, "adj_dropedge: p %g outside [0, 1)", (double)p);  // (a NaN fails both comparisons)
+    SEG_REQUIRE(rowptr && col && w, "adj_dropedge: null forward CSR (rowptr, col, w)");
+    SEG_REQUIRE(rowptr_t && col_t && w_t, "adj_dropedge: null transposed CSR (rowptr_t, col_t, w_t)");
+    SEG_REQUIRE(rng, "adj_dropedge: null rng (the device (seed, step) words)");
+    SEG_REQUIRE(deg && val && val_t, "adj_dropedge: null output (deg, val, val_t)");
+    if (n_rows == 0) return 0;
+    return glass::adj_dropedge_launch(rowptr, col, w, rowptr_t, col_t, w_t, n_rows, aggr, p, symmetric, rng, call_id, deg, val,
+                                      val_t, keep, stream);
+}

@@ -201,6 +201,8 @@ class CSRAdj:
         self.perm = perm  # entry e of the forward CSR is edge perm[e] of the caller's edge_index (int64, as argsort left it)
         self.fwd = CSROperand(rowptr, col32, val, n, n)
         self.bwd = CSROperand(rowptr_t, col_t, val_t, n, n)
+        if aggr in _lib.AGGR_MODES:
+            self._raw_w = val if aggr == "sum" else w  # the raw weights, forward entry order (edge dropout redraws from them)
         if aggr in ("max", "gat", "pna"):
             self.eid_t = perm_t.to(torch.int32).contiguous()  # transposed entry t is forward entry eid_t[t]
         if aggr in _RAW_AGGR:
@@ -322,6 +324,69 @@ class CSRAdj:
                                                   torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "glass_adj_values_bwd_f32")
         return dw
+
+    # ---- K2d: edge dropout (aggr "sum", "mean", "gcn"; csrc/spmm_dropedge.hip) -------------------------------------------------
+    def _dropedge_state(self, what):
+        """(raw weights in forward order, raw weights in transposed order, buffers), built the first time edge dropout asks.  The
+        transposed-order weights of "sum" are the stored backward values; "mean" and "gcn" permute the raw forward weights once
+        with the transpose's stable sort (the same permutation the constructor used)."""
+        if self.aggr not in _lib.AGGR_MODES:
+            raise _lib.GlassHipError(f"CSRAdj.{what}: no edge dropout for aggr {self.aggr!r} (only 'sum', 'mean', 'gcn': the others "
+                                     "need the entry excluded, not weighted zero)")
+        st = self.__dict__.get("_dropedge")
+        if st is None:
+            if self.aggr == "sum":
+                w_t = self.bwd.val
+            else:
+                eid_t = self._edge_grad_state(what)[0]
+                w_t = self._raw_w[eid_t.to(torch.int64)].contiguous()
+            st = self._dropedge = (self._raw_w, w_t, {})
+        return st
+
+    def dropedge_values(self, p, call_id, symmetric=True, want_keep=False, rng=None):
+        """(val, val_t, deg[, keep]) under edge dropout at rate p: one keep bit per entry drawn by K2d from (seed, step, call_id,
+        destination, source, N) — `rng` the int64[2] (seed, step) words on the device, default ops.rng_tensor — the dropped
+        entries' weights set to +0.0, and K2's values for those weights on the unchanged structure: the bits of
+        values_of(w * keep).  keep: uint8 [nnz] in FORWARD ENTRY order (entry e is the caller's edge perm[e]).
+        The results live in one set of buffers per (call_id, workspace branch), overwritten by the next call with that key: a
+        captured graph keeps launching on them (their sizes never change, so none is ever replaced or handed back).
+        `dropedge_record(call_id)["gen"]` counts the draws into the current key's buffers."""
+        w, w_t, bufs = self._dropedge_state("dropedge_values")
+        p = float(p)
+        if not (0.0 <= p < 1.0):
+            raise ValueError(f"edge dropout rate must lie in [0, 1), got {p!r}")
+        op, dev = self.fwd, self.fwd.rowptr.device
+        key = (int(call_id), _ws_branch)
+        b = bufs.get(key)
+        if b is None:
+            e = max(op.nnz, 1)
+            b = bufs[key] = {"val": torch.empty(e, dtype=torch.float32, device=dev)[:op.nnz],
+                             "val_t": torch.empty(e, dtype=torch.float32, device=dev)[:op.nnz],
+                             "deg": torch.empty(self.n_node, dtype=torch.float32, device=dev), "keep": None, "gen": 0}
+        if want_keep and b["keep"] is None:
+            b["keep"] = torch.empty(max(op.nnz, 1), dtype=torch.uint8, device=dev)[:op.nnz]
+        b["gen"] += 1
+        if op.nnz == 0:
+            b["deg"].fill_(1.0)  # K2's rule on an empty row
+        else:
+            if rng is None:
+                from . import ops
+                rng = ops.rng_tensor(dev)
+            assert rng.dtype == torch.int64 and rng.numel() == 2 and rng.device == dev
+            rc = _lib.load().glass_adj_dropedge_f32(op.rowptr.data_ptr(), op.col.data_ptr(), w.data_ptr(), self.bwd.rowptr.data_ptr(),
+                                                    self.bwd.col.data_ptr(), w_t.data_ptr(), self.n_node, _lib.AGGR_MODES[self.aggr],
+                                                    p, 1 if symmetric else 0, rng.data_ptr(), int(call_id), b["deg"].data_ptr(),
+                                                    b["val"].data_ptr(), b["val_t"].data_ptr(),
+                                                    b["keep"].data_ptr() if want_keep else None,
+                                                    torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "glass_adj_dropedge_f32")
+        out = (b["val"], b["val_t"], b["deg"])
+        return out + (b["keep"], ) if want_keep else out
+
+    def dropedge_record(self, call_id):
+        """The record of the buffers of (call_id, current workspace branch), after a draw into them: its "gen" counts the draws
+        so far — a holder of the tensors knows from it whether they still hold ITS draw."""
+        return self._dropedge_state("dropedge_record")[2][(int(call_id), _ws_branch)]
 
     def _need_max(self, what):
         if self.aggr != "max":

@@ -196,8 +196,37 @@ def set_live_edge_weight(emb):
         if getattr(c, "aggr", None) not in ("sum", "mean", "gcn") or not isinstance(c, GLASSConv):
             raise ValueError(f"live_edge_weight needs GLASSConv layers with aggr 'sum', 'mean' or 'gcn', not "
                              f"{type(c).__name__} with aggr {getattr(c, 'aggr', None)!r}")
+        if getattr(c, "edge_dropout", 0.0) > 0:
+            raise ValueError("live_edge_weight is not available together with edge_dropout")
     for c in emb.convs:
         c.live_edge_weight = True
+
+
+def _check_edge_dropout(p, aggr, live_edge_weight):
+    """The edge dropout rate as a float, or ValueError: outside [0, 1); > 0 with an aggregation other than "sum" / "mean" / "gcn"
+    (those need the entry excluded, not weighted zero) or together with live_edge_weight."""
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= float(p) < 1.0):
+        raise ValueError(f"GLASSConv: edge_dropout must be a number in [0, 1), not {p!r}")
+    p = float(p)
+    if p > 0 and aggr not in ("sum", "mean", "gcn"):
+        raise ValueError(f"GLASSConv: edge_dropout needs aggr 'sum', 'mean' or 'gcn', not {aggr!r} (the other aggregations "
+                         "need a dropped entry excluded, not weighted zero)")
+    if p > 0 and live_edge_weight:
+        raise ValueError("GLASSConv: edge_dropout is not available together with live_edge_weight")
+    return p
+
+
+def set_edge_dropout(emb, p, symmetric=None):
+    """Every GLASSConv layer of `emb` to edge dropout rate p (what their constructor argument sets; ValueError, before any layer
+    is changed, where a layer's constructor would refuse it).  symmetric: None keeps each layer's key mode."""
+    for c in emb.convs:
+        if not isinstance(c, GLASSConv):
+            raise ValueError(f"edge_dropout needs GLASSConv layers, not {type(c).__name__}")
+        _check_edge_dropout(p, c.aggr, c.live_edge_weight)
+    for c in emb.convs:
+        c.edge_dropout = float(p)
+        if symmetric is not None:
+            c.edge_dropout_symmetric = bool(symmetric)
 
 
 class GLASSConv(nn.Module):
@@ -219,14 +248,26 @@ class GLASSConv(nn.Module):
     delta / log(W + 1) (W the node's weight sum, delta the graph's mean of log(W + 1)), the twelve views weighted per channel
     by the layer's parameter pna_weight [12, out_channels] (1 / 12 each at the start: the widths do not change, and PNA's
     dense post-tower is the comb pair this layer already has).  The state_dict is that of aggr "mean" plus `pna_weight`; one
-    graph at a time (ValueError with `batch` or live_edge_weight)."""
+    graph at a time (ValueError with `batch` or live_edge_weight).
+    edge_dropout=p (an extension, DropEdge; 0 <= p < 1, aggr "sum" / "mean" / "gcn" only, not with live_edge_weight or `batch`:
+    ValueError otherwise): every TRAINING forward draws one keep bit per adjacency entry on the GPU (ops.spmm_dropedge, stream
+    call_base + 2: each layer its own mask, a new one every step) and aggregates with the normalisation of the surviving
+    weights; edge_dropout_symmetric (default True) gives both directions of an undirected edge, and parallel duplicates, one
+    fate.  There is NO 1 / (1 - p) rescale (PyG's dropout_edge has none): "mean" and "gcn" renormalise by construction, "sum"
+    does not — its aggregate shrinks by 1 - p in expectation.  A dropped entry stays in the structure at weight +0.0, so a
+    non-finite source row still propagates, as at a stored weight of 0.  In eval mode or at p == 0 nothing is drawn or launched
+    and the results are bit for bit those of a layer without the argument; no parameter, the same state_dict.  Such a layer
+    runs as per-op autograd nodes (the stack program declines its model)."""
     def __init__(self, in_channels: int, out_channels: int, activation=nn.ReLU(inplace=True), aggr="mean",
-                 z_ratio=0.8, dropout=0.2, softmax_t=1.0, gat_slope=0.2, gat_heads=1, live_edge_weight=False, moment_eps=1e-5):
+                 z_ratio=0.8, dropout=0.2, softmax_t=1.0, gat_slope=0.2, gat_heads=1, live_edge_weight=False, moment_eps=1e-5,
+                 edge_dropout=0.0, edge_dropout_symmetric=True):
         super().__init__()
         if live_edge_weight and aggr not in ("sum", "mean", "gcn"):
             raise ValueError(f"GLASSConv: live_edge_weight needs aggr 'sum', 'mean' or 'gcn', not {aggr!r} (no edge-weight "
                              "gradient for the other aggregations)")
         self.live_edge_weight = bool(live_edge_weight)
+        self.edge_dropout = _check_edge_dropout(edge_dropout, aggr, self.live_edge_weight)
+        self.edge_dropout_symmetric = bool(edge_dropout_symmetric)
         self.trans_fns = nn.ModuleList([nn.Linear(in_channels, out_channels), nn.Linear(in_channels, out_channels)])
         self.comb_fns = nn.ModuleList([nn.Linear(in_channels + out_channels, out_channels),
                                        nn.Linear(in_channels + out_channels, out_channels)])
@@ -272,6 +313,9 @@ class GLASSConv(nn.Module):
             raise ValueError("GLASSConv: live_edge_weight has no replicated form (exact zero-one labels: `batch` given)")
         if self.aggr in ("std", "var", "pna") and batch is not None:
             raise ValueError(f"GLASSConv: aggr {self.aggr!r} has no replicated form (exact zero-one labels: `batch` given)")
+        p_edge = _check_edge_dropout(self.edge_dropout, self.aggr, self.live_edge_weight)  # (the attributes may have been set since)
+        if p_edge > 0 and batch is not None:
+            raise ValueError("GLASSConv: edge_dropout has no replicated form (exact zero-one labels: `batch` given)")
         if self.adj is None:
             self.adj = buildAdj(edge_index, edge_weight.detach() if self.live_edge_weight else edge_weight,
                                 x_.shape[0] if batch is None else batch.N, self.aggr)
@@ -279,6 +323,9 @@ class GLASSConv(nn.Module):
             raise ValueError(f"GLASSConv: {x_.shape[0]} rows for {batch!r}")
         if self.live_edge_weight:
             agg = lambda m: ops.spmm_w(self.adj, m, edge_weight)
+        elif self.training and p_edge > 0:
+            # (call_base + 0 and + 1 are the two GraphNorm streams of this layer)
+            agg = lambda m: ops.spmm_dropedge(self.adj, m, p_edge, self.call_base + 2, self.edge_dropout_symmetric)
         elif batch is not None:
             agg = lambda m: ops.spmm_rep(self.adj, m, batch.R)
         elif self.aggr == "softmax":
@@ -399,7 +446,7 @@ class EmbZGConv(nn.Module):
             # the whole stack as one autograd node (explicit forward / backward program, glass_amd/stack.py)
             return stack.run(self, x_flat, z, edge_index, edge_weight)
         p = self.dropout if self.training else 0.0
-        if self.training and (p > 0 or any(c.dropout > 0 for c in self.convs)):
+        if self.training and (p > 0 or any(c.dropout > 0 or getattr(c, "edge_dropout", 0.0) > 0 for c in self.convs)):
             ops.rng_advance(x.device)  # new dropout masks for this forward/backward pair
             # ... read from a private snapshot of the (seed, step) words by this forward's ops and by their backward, so
             # further training forwards may come before it (NodeEmb over several channels, gradient accumulation)

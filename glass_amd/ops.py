@@ -445,6 +445,70 @@ def spmm_w(adj, x, w):
     return SpMMWFn.apply(adj, x, w)
 
 
+class SpMMDropFn(torch.autograd.Function):
+    """y = A' @ x with A' the adjacency under edge dropout (DropEdge; K2d, CSRAdj.dropedge_values: one keep bit per entry from the
+    dropout words of this pass, the dropped entries at weight +0.0, K2's normalisation of the masked weights); backward
+    dx = A'^T @ dy on K1 with the transposed values of the SAME draw.  The mask is a constant: no gradient to the weights.
+    The draw's values live in the adjacency's per-call_id buffers, which the next draw of that call_id overwrites; the backward
+    uses them as they are when no draw has come in between (always so inside a captured step) and otherwise draws again from
+    the words its forward read."""
+    @staticmethod
+    def forward(ctx, adj, x, p, call_id, symmetric):
+        _need_gpu(x)
+        x, _ = _rows(x)
+        words = rng_tensor(x.device)  # this pass's (seed, step): a redraw in the backward re-reads THESE
+        val, val_t, _deg = adj.dropedge_values(p, call_id, symmetric, rng=words)
+        ctx.adj, ctx.cfg, ctx.rng_words = adj, (p, call_id, symmetric), words
+        ctx.rec = adj.dropedge_record(call_id)  # the buffers' record: its "gen" counts the draws that went into them
+        ctx.val_t, ctx.gen = val_t, ctx.rec["gen"]
+        ctx.rng_epoch = rng_epoch(x.device)
+        return adj.fwd.spmm(x, val=val)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy, _ = _rows(dy)
+        adj = ctx.adj
+        p, call_id, symmetric = ctx.cfg
+        val_t = ctx.val_t
+        if ctx.rec["gen"] != ctx.gen:  # another draw has overwritten the buffers since the forward
+            if ctx.rng_words is rng_state(dy.device):  # no snapshot was taken: the live words must be unchanged
+                check_rng_epoch(dy.device, ctx.rng_epoch, "SpMMDropFn.backward")
+            val_t = adj.dropedge_values(p, call_id, symmetric, rng=ctx.rng_words)[1]
+        return None, adj.bwd.spmm(dy, val=val_t), None, None, None
+
+
+def _dropedge_args(adj, p, what):
+    aggr = getattr(adj, "aggr", None)
+    if aggr not in _lib.AGGR_MODES:
+        raise GlassHipError(f"{what}: no edge dropout for aggr {aggr!r} (only 'sum', 'mean', 'gcn')")
+    p = float(p)
+    if not (0.0 <= p < 1.0):
+        raise ValueError(f"{what}: the edge dropout rate must lie in [0, 1), got {p!r}")
+    return p
+
+
+def spmm_dropedge(adj, x, p, call_id, symmetric=True):
+    """Aggregation under edge dropout: `adj` a graph.CSRAdj built for aggr "sum", "mean" or "gcn".  Every call draws one keep
+    bit per adjacency entry from (rng_tensor's (seed, step), call_id, destination, source, N) — with symmetric=True the two
+    directions of an undirected edge, and parallel duplicates, share one bit — and aggregates with K2's values of the masked
+    weights: the bits of ops.spmm_w(adj, x, w * keep), differentiable in x only.  No 1 / (1 - p) rescale (as PyG's
+    dropout_edge): "mean" and "gcn" renormalise by construction, "sum" does NOT — its expected output shrinks by 1 - p.  A dropped
+    entry stays in the structure at value +0.0: K1 still gathers its source row, so a non-finite source row propagates as it
+    does at a stored weight of 0."""
+    p = _dropedge_args(adj, p, "spmm_dropedge")
+    return SpMMDropFn.apply(adj, x, p, int(call_id), bool(symmetric))
+
+
+def edge_keep_mask(adj, p, call_id, symmetric=True):
+    """uint8 [E] in the order of the edge_index `adj` was built from: the keep bits ops.spmm_dropedge(adj, x, p, call_id,
+    symmetric) draws at the CURRENT dropout words (rng_tensor).  A copy of its own: later draws do not change it."""
+    p = _dropedge_args(adj, p, "edge_keep_mask")
+    keep = adj.dropedge_values(p, int(call_id), bool(symmetric), want_keep=True)[3]
+    out = torch.empty_like(keep)
+    out[adj.perm] = keep
+    return out
+
+
 def spmm(adj, x):
     if getattr(adj, "aggr", None) == "max":
         return SpMMMaxFn.apply(adj, x)

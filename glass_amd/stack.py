@@ -621,6 +621,8 @@ class StackProgram:
             return False
         if any(getattr(c, "live_edge_weight", False) for c in emb.convs):
             return False  # live edge weights (ops.spmm_w): the program bakes the adjacency's stored values in
+        if any(getattr(c, "edge_dropout", 0.0) > 0 for c in emb.convs):
+            return False  # edge dropout (ops.spmm_dropedge): new adjacency values every step, the program reads the stored ones
         if isinstance(emb, EmbGConv):
             return StackProgram.supported_unlabeled(emb)
         if not ops.USE_FUSED_DENSE or getattr(emb, "_glass_arena", None) is None or emb.gns is None:

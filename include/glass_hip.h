@@ -430,6 +430,24 @@ int glass_adj_values_bwd_f32(const int32_t* rowptr, const int32_t* col, const in
                              const float* dval, const float* R, const float* C, int64_t n_rows, int64_t nnz, int aggr,
                              float* dw /*[nnz], caller's edge order*/, void* stream);
 
+/* K2d edge dropout (DropEdge; an extension: csrc/spmm_dropedge.hip) for the three aggregations of K2.  One keep bit per entry
+ *     (i = destination row, j = source column) of an n_rows x n_rows adjacency:
+ *       key = symmetric ? min(i,j) * n_rows + max(i,j) : i * n_rows + j   (uint64)
+ *       u   = float(rand4(rng[0], rng[1], call_id, key)[0] >> 8) * 2^-24;  kept iff u >= p   (the dropout kernels' rule)
+ *     a function of (seed, step, call_id, i, j, n_rows) alone: the transposed CSR draws the same bit from its own indices.  With
+ *     w' = kept ? w : +0.0f on the unchanged structure, deg / val / val_t receive what glass_adj_values_f32 leaves for w' (deg,
+ *     val) and the same values in the transposed CSR's entry order (val_t), BIT FOR BIT: the degree pass adds in K2's order.
+ *     (w, w_t: the raw weights in forward / transposed entry order.)  keep (optional, may be null): the bits as bytes, forward
+ *     entry order.  rng: int64[2] = (seed, step) in DEVICE memory, read by the kernels (a captured graph draws fresh masks).
+ *     Two launches (masked degree; values of both CSRs), one for sum; no atomics, bitwise repeatable.  Refused on the host before
+ *     any HIP call: unknown aggr -> GLASS_E_UNSUPPORTED; n_rows outside [0, 2^31 - 1), p outside [0, 1), a null pointer other
+ *     than keep -> GLASS_E_ARG.  n_rows == 0 returns 0 without a launch. */
+int glass_adj_dropedge_f32(const int32_t* rowptr, const int32_t* col, const float* w,          /* CSR of A, raw weights */
+                           const int32_t* rowptr_t, const int32_t* col_t, const float* w_t,    /* CSR of A^T, raw weights */
+                           int64_t n_rows, int aggr, float p, int symmetric, const int64_t* rng, uint64_t call_id,
+                           float* deg /*[n_rows]*/, float* val /*[nnz]*/, float* val_t /*[nnz]*/, uint8_t* keep /*[nnz] or null*/,
+                           void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * K4  max-zero-one label   replaces utils.MaxZOZ (impl/utils.py:32-45):  z[n]=0; z[pos>=0]=1
  * ---------------------------------------------------------------------------------------- */
