@@ -17,6 +17,13 @@ aggr "max", "softmax", "gat", "std", "var" and "pna" keep the raw edge weights i
 require them > 0.
 Duplicate (row,col) entries are kept as separate entries: they add up in the product exactly as in
 the reference's uncoalesced COO matmul.
+
+Every entry that walks a CSR takes `rowptr, col, val[, eid_t]`, its own operands, then `n_rows[, H[, K]]`, trailing scalars,
+and `header, plan, ws, stream`: `_launch` is the one place that puts that list together, sizes and fetches the workspace, and
+checks the return code.  `_call` (under it, and under the entries without a CSR) refuses a call whose argument count is not
+the entry's — ctypes itself lets extra arguments through.  Workspaces come from one grow-or-retire cache (`_Workspaces`):
+every matrix has one for its product, the adjacencies of the extensions one for their kernels, and the edge-weight path one
+made with the rest of its state on first use.
 """
 import ctypes
 
@@ -24,6 +31,82 @@ import numpy as np
 import torch
 
 from . import _lib
+
+_ws_branch = 0
+
+
+def set_workspace_branch(b):
+    """Which workspace set CSROperand.workspace hands out from now on (0: the default one)."""
+    global _ws_branch
+    _ws_branch = int(b)
+
+
+class _Workspaces(dict):
+    """The kernels' scratch (partial rows, pairs and triples of rows cut into several chunks; fp64 partials): the live buffers,
+    one 8-byte aligned buffer of at least 16 bytes per (entry, width, BRANCH) — entry the launch method's name, width (H, ) or
+    (H, K); set_workspace_branch: concurrent launches on the same matrix, the parallel evaluation branches of
+    evalstep.EvalGraph, must not share one.  A request that fits gets the SAME tensor again; a larger one gets a new tensor and
+    the old one goes to `retired`, never freed or handed out again: a captured graph may still launch with its pointer."""
+    def __init__(self, device):
+        super().__init__()
+        self.device, self.retired = device, []
+
+    def fetch(self, entry, width, nbytes):
+        """nbytes: the answer of the entry's *_ws_bytes query (negative: it refused the plan header)"""
+        if nbytes < 0:
+            raise _lib.GlassHipError("bad plan header")
+        key = (entry, width, _ws_branch)
+        ws = self.get(key)
+        if ws is None or ws.numel() * 8 < nbytes:
+            if ws is not None:
+                self.retired.append(ws)
+            ws = self[key] = torch.empty(max((nbytes + 7) // 8, 2), dtype=torch.float64, device=self.device)
+        return ws
+
+
+def _call(fn, entry, args):
+    """The return code of the library's `entry` (fn) on `args` and the current stream (looked up now: a launch goes where the
+    caller is working).  The count is held to the entry's row of _lib.SIGNATURES — what load() gave fn as argtypes; fn itself
+    may be a plain wrapper without them (bench.py's instrumented pass brackets every entry in one)."""
+    want = len(_lib.SIGNATURES[entry][1])
+    if len(args) + 1 != want:
+        raise _lib.GlassHipError(f"{entry}: called with {len(args) + 1} arguments, the entry takes {want}")
+    return fn(*args, torch.cuda.current_stream().cuda_stream)
+
+
+def _run(entry, args):
+    _lib.check(_call(getattr(_lib.load(), entry), entry, args), entry)
+
+
+def _launch(op, cache, key, entry, query, mid, H=None, K=None, eid_t=None, tail=(), val=None, header=None):
+    """One CSR entry on the matrix `op` (a CSROperand): entry(rowptr, col, val[, eid_t], *mid, n_rows[, H[, K]], *tail, header,
+    plan, ws, stream) with ws from `cache` under `key` (the launch method's name) at the size `query`(header[, H[, K]]) names.
+    val / header: others than op's own (same entries, same plan).  Returns the workspace."""
+    lib = _lib.load()
+    hdr = (op.header if header is None else header).ctypes.data
+    width = () if H is None else (H, ) if K is None else (H, K)
+    ws = cache.get((key, width, _ws_branch))
+    if ws is None:  # (these sizes are functions of the plan and the width alone: asked once per key)
+        ws = cache.fetch(key, width, getattr(lib, query)(hdr, *width))
+    args = [op.rowptr.data_ptr(), op.col.data_ptr(), (op.val if val is None else val).data_ptr()]
+    if eid_t is not None:
+        args.append(eid_t.data_ptr())
+    args += mid
+    args += (op.n_rows, *width, *tail, hdr, op.plan.data_ptr(), ws.data_ptr())
+    _lib.check(_call(getattr(lib, entry), entry, args), entry)
+    return ws
+
+
+def _operand(a, n, name, dtype=torch.float32):
+    """The leading dimension of a row-major [n, H] operand on the device: its row stride, and for a single row at least H."""
+    assert a.dim() == 2 and a.stride(1) == 1 and a.dtype == dtype and a.is_cuda, name
+    assert a.shape[0] == n, f"{name} has {a.shape[0]} rows, the adjacency has {n} nodes"
+    return a.stride(0) if a.shape[0] > 1 else max(a.shape[1], a.stride(0))
+
+
+def _empty(like, *shape, dtype=torch.float32):
+    return torch.empty(shape, dtype=dtype, device=like.device)
+
 
 class CSROperand:
     """One CSR matrix + its K1 plan; `spmm` enqueues Y = M @ X on the current stream."""
@@ -47,25 +130,18 @@ class CSROperand:
             self.plan = torch.from_numpy(plan).to(rowptr.device)
         else:
             self.plan = torch.from_numpy(plan).pin_memory().to(rowptr.device, non_blocking=True)
-        self._ws = {}
-        self._retired_ws = []
+        self._ws = _Workspaces(rowptr.device)
 
     @property
     def nnz(self):
         return int(self.header[3])
 
     def workspace(self, H):
-        """Partial-row scratch of products with rows cut into several chunks: one buffer per feature width and per BRANCH
-        (set_workspace_branch: concurrent products on the same matrix — the parallel evaluation branches of
-        evalstep.EvalGraph — must not share it)."""
-        key = (H, _ws_branch)
-        ws = self._ws.get(key)
+        """Partial-row scratch of products with rows cut into several chunks (the buffer `spmm` launches with): one per feature
+        width and per branch."""
+        ws = self._ws.get(("spmm", (H, ), _ws_branch))
         if ws is None:
-            nbytes = _lib.load().glass_spmm_ws_bytes(self.header.ctypes.data, H)
-            if nbytes < 0:
-                raise _lib.GlassHipError("bad plan header")
-            ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=self.rowptr.device)
-            self._ws[key] = ws
+            ws = self._ws.fetch("spmm", (H, ), _lib.load().glass_spmm_ws_bytes(self.header.ctypes.data, H))
         return ws
 
     def spmm(self, x, out=None, val=None):
@@ -79,11 +155,9 @@ class CSROperand:
         if val is None:
             val = self.val
         assert val.dtype == torch.float32 and val.shape == self.val.shape and val.is_contiguous() and val.device == self.val.device
-        rc = _lib.load().glass_spmm_csr_f32(self.rowptr.data_ptr(), self.col.data_ptr(), val.data_ptr(),
-                                            x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), self.n_rows, H,
-                                            self.header.ctypes.data, self.plan.data_ptr(),
-                                            self.workspace(H).data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_csr_f32")
+        # (the row strides as they are: no single-row rule here)
+        _launch(self, self._ws, "spmm", "glass_spmm_csr_f32", "glass_spmm_ws_bytes",
+                (x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0)), H, val=val)
         return out
 
     def spmm_rep(self, x, R, x_rep_stride=None, out=None, y_rep_stride=None):
@@ -100,20 +174,15 @@ class CSROperand:
             out = torch.empty((R * ys, H), dtype=torch.float32, device=x.device)
         assert out.stride(1) == 1 and out.shape[1] == H and (R == 0 or out.shape[0] >= (R - 1) * ys + self.n_rows)
         lib = _lib.load()
-        key = ("rep", H, _ws_branch)  # one buffer per width, grown when a call needs more replicas' partial rows
-        nbytes = lib.glass_spmm_rep_ws_bytes(self.header.ctypes.data, H, R)
-        if nbytes < 0:
-            raise _lib.GlassHipError("bad plan header")
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() * 4 < nbytes:
-            if ws is not None:
-                self._retired_ws.append(ws)  # (a captured graph may still launch with this pointer: never handed back)
-            ws = self._ws[key] = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=self.rowptr.device)
+        hdr = self.header.ctypes.data
+        # not through _launch: one buffer per width (not per R), grown when a call needs more replicas' partial rows, and a
+        # return code with an answer of its own
+        ws = self._ws.fetch("rep", (H, ), lib.glass_spmm_rep_ws_bytes(hdr, H, R))
         ldx = x.stride(0) if x.shape[0] > 1 else max(H, x.stride(0))
         ldy = out.stride(0) if out.shape[0] > 1 else max(H, out.stride(0))
-        rc = lib.glass_spmm_csr_rep_f32(self.rowptr.data_ptr(), self.col.data_ptr(), self.val.data_ptr(), x.data_ptr(), ldx, xs,
-                                        out.data_ptr(), ldy, ys, self.n_rows, H, R, self.header.ctypes.data,
-                                        self.plan.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        rc = _call(lib.glass_spmm_csr_rep_f32, "glass_spmm_csr_rep_f32",
+                   (self.rowptr.data_ptr(), self.col.data_ptr(), self.val.data_ptr(), x.data_ptr(), ldx, xs, out.data_ptr(), ldy, ys,
+                    self.n_rows, H, R, hdr, self.plan.data_ptr(), ws.data_ptr()))
         if rc == -3:  # GLASS_E_UNSUPPORTED: too many replicas, or too much memory, for one launch
             msg = lib.glass_last_error_string().decode(errors="replace")
             raise _lib.GlassHipError(f"glass_spmm_csr_rep_f32: {msg}; run the replicas in smaller groups (EmbZGConv.replica_chunk)")
@@ -141,19 +210,14 @@ def _pna_degrees(rowptr, w):
     return delta, torch.from_numpy(W.astype(np.float32)).to(rowptr.device)
 
 
-_ws_branch = 0
 _RAW_AGGR = ("max", "softmax", "gat", "std", "var", "pna")  # the extensions: raw edge weights in val, kernels of their own
 MOMENT_KINDS = {"std": 0, "var": 1}
 
 
-def set_workspace_branch(b):
-    """Which workspace set CSROperand.workspace hands out from now on (0: the default one)."""
-    global _ws_branch
-    _ws_branch = int(b)
-
-
 class CSRAdj:
-    """Normalised adjacency A (forward) and A^T (backward) for one aggregation scheme.  aggr "max" (an extension): the raw
+    """Normalised adjacency A (forward) and A^T (backward) for one aggregation scheme.  Every launch method below is a guard
+    on the aggr the adjacency was built for (`_need`), the operands' leading dimensions (`_operand`), the results, and one
+    `_launch` on `fwd` or `bwd` with a workspace from `_aggr_ws`.  aggr "max" (an extension): the raw
     edge weights (the values of "sum"), aggregated by K1m (max_fwd / max_bwd) instead of K1's product.  aggr "softmax" (an
     extension): the raw weights too, strictly positive (checked here, once), aggregated by K1s (softmax_fwd / softmax_bwd /
     softmax_dt) with a temperature the caller owns.  aggr "gat" (an extension): built like "softmax", aggregated by K1a
@@ -187,11 +251,8 @@ class CSRAdj:
         col32 = col.to(torch.int32).contiguous()
         self.deg = torch.empty(n, dtype=torch.float32, device=dev)
         val = torch.empty(nnz, dtype=torch.float32, device=dev)
-        rc = _lib.load().glass_adj_values_f32(rowptr.data_ptr(), col32.data_ptr(), w.data_ptr(), n,
-                                              _lib.AGGR_MODES["sum" if aggr in _RAW_AGGR else aggr], self.deg.data_ptr(),
-                                              val.data_ptr(),
-                                              torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_adj_values_f32")
+        _run("glass_adj_values_f32", (rowptr.data_ptr(), col32.data_ptr(), w.data_ptr(), n,
+                                      _lib.AGGR_MODES["sum" if aggr in _RAW_AGGR else aggr], self.deg.data_ptr(), val.data_ptr()))
         # transpose: same entries keyed by (col,row); values are permuted, never recomputed
         perm_t = torch.argsort(col * n + row, stable=True)
         rowptr_t = _csr_from_sorted(col[perm_t], n)
@@ -206,8 +267,7 @@ class CSRAdj:
         if aggr in ("max", "gat", "pna"):
             self.eid_t = perm_t.to(torch.int32).contiguous()  # transposed entry t is forward entry eid_t[t]
         if aggr in _RAW_AGGR:
-            self._aggr_ws = {}
-            self._retired_ws = []
+            self._aggr_ws = _Workspaces(dev)
         if aggr == "pna":
             self.pna_delta, self.pna_wsum = _pna_degrees(rowptr, w)
 
@@ -215,18 +275,10 @@ class CSRAdj:
     def nnz(self):
         return self.fwd.nnz
 
-    def _aggr_workspace(self, entry, H, nbytes):
-        """Workspaces of K1m, K1s, K1a, K1v and K1p (partial pairs / triples / rows of cut rows, the fp64 partials of "softmax_dt" and "gat_datt"): one
-        8-byte aligned buffer per entry, feature width and branch (set_workspace_branch)."""
-        if nbytes < 0:
-            raise _lib.GlassHipError("bad plan header")
-        key = (entry, H, _ws_branch)
-        ws = self._aggr_ws.get(key)
-        if ws is None or ws.numel() * 8 < nbytes:
-            if ws is not None:
-                self._retired_ws.append(ws)  # (a captured graph may still launch with this pointer: never handed back)
-            ws = self._aggr_ws[key] = torch.empty(max((nbytes + 7) // 8, 2), dtype=torch.float64, device=self.fwd.rowptr.device)
-        return ws
+    def _need(self, what, *aggrs):
+        if self.aggr not in aggrs:
+            raise _lib.GlassHipError(f"CSRAdj.{what}: this adjacency was built for aggr {self.aggr!r}, not "
+                                     + " or ".join(repr(a) for a in aggrs))
 
     # ---- K1w: the gradient with respect to the edge weights (aggr "sum", "mean", "gcn"; csrc/spmm_edge.hip) -----------------
     def _edge_grad_state(self, what):
@@ -239,18 +291,8 @@ class CSRAdj:
             rp = self.fwd.rowptr.to(torch.int64)
             row = torch.repeat_interleave(torch.arange(self.n_node, device=rp.device), rp[1:] - rp[:-1])
             eid_t = torch.argsort(self.fwd.col.to(torch.int64) * self.n_node + row, stable=True).to(torch.int32).contiguous()
-            st = self._edge_grad = (eid_t, self.perm.to(torch.int32).contiguous(), {})
+            st = self._edge_grad = (eid_t, self.perm.to(torch.int32).contiguous(), _Workspaces(rp.device))
         return st
-
-    def _edge_ws(self, key, nbytes):
-        if nbytes < 0:
-            raise _lib.GlassHipError("bad plan header")
-        pool = self._edge_grad_state("workspace")[2]
-        key = (key, _ws_branch)
-        ws = pool.get(key)
-        if ws is None:
-            ws = pool[key] = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=self.fwd.rowptr.device)
-        return ws
 
     def values_of(self, w):
         """(val, val_t, deg) for the caller-order weight vector w (fp32 [E] on the device, the order of the edge_index this
@@ -262,47 +304,37 @@ class CSRAdj:
             raise ValueError(f"edge weights: expected {op.nnz} fp32 on {op.rowptr.device}, got {tuple(w.shape)} {w.dtype} on {w.device}")
         eid_t, _p, _ws = self._edge_grad_state("values_of")
         ws = w.detach()[self.perm].contiguous()
-        deg = torch.empty(self.n_node, dtype=torch.float32, device=w.device)
-        val = torch.empty(op.nnz, dtype=torch.float32, device=w.device)
-        rc = _lib.load().glass_adj_values_f32(op.rowptr.data_ptr(), op.col.data_ptr(), ws.data_ptr(), self.n_node,
-                                              _lib.AGGR_MODES[self.aggr], deg.data_ptr(), val.data_ptr(),
-                                              torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_adj_values_f32")
+        deg = _empty(w, self.n_node)
+        val = _empty(w, op.nnz)
+        _run("glass_adj_values_f32", (op.rowptr.data_ptr(), op.col.data_ptr(), ws.data_ptr(), self.n_node,
+                                      _lib.AGGR_MODES[self.aggr], deg.data_ptr(), val.data_ptr()))
         return val, val[eid_t.to(torch.int64)].contiguous(), deg
 
     def dval(self, dy, x, val):
         """(dval, R) = the sampled dense-dense product over the forward CSR: dval [nnz] the dot of dy[destination] and
         x[source] of every entry, in forward entry order; R [N] the row sums of dval * val."""
-        self._edge_grad_state("dval")
+        _e, _p, cache = self._edge_grad_state("dval")
         op = self.fwd
-        ldx = self._softmax_operand(x, op.n_cols, "X")
-        lddy = self._softmax_operand(dy, op.n_rows, "dY")
+        ldx = _operand(x, op.n_cols, "X")
+        lddy = _operand(dy, op.n_rows, "dY")
         assert dy.shape == x.shape
         assert val.dtype == torch.float32 and val.shape == (op.nnz, ) and val.is_contiguous() and val.is_cuda
         H = x.shape[1]
-        lib = _lib.load()
-        dv = torch.empty(max(op.nnz, 1), dtype=torch.float32, device=x.device)[:op.nnz]
-        R = torch.empty(op.n_rows, dtype=torch.float32, device=x.device)
-        ws = self._edge_ws("dval", lib.glass_spmm_dval_ws_bytes(op.header.ctypes.data, H))
-        rc = lib.glass_spmm_dval_f32(op.rowptr.data_ptr(), op.col.data_ptr(), val.data_ptr(), x.data_ptr(), ldx, dy.data_ptr(),
-                                     lddy, dv.data_ptr(), R.data_ptr(), op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
-                                     ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_dval_f32")
+        dv = _empty(x, max(op.nnz, 1))[:op.nnz]
+        R = _empty(x, op.n_rows)
+        _launch(op, cache, "dval", "glass_spmm_dval_f32", "glass_spmm_dval_ws_bytes",
+                (x.data_ptr(), ldx, dy.data_ptr(), lddy, dv.data_ptr(), R.data_ptr()), H, val=val)
         return dv, R
 
     def colsum(self, dval, val_t):
         """C [N] = the column sums of dval * val, over the transposed CSR (aggr "gcn" needs them)."""
-        eid_t, _p, _ws = self._edge_grad_state("colsum")
+        eid_t, _p, cache = self._edge_grad_state("colsum")
         op = self.bwd
         for a in (dval, val_t):
             assert a.dtype == torch.float32 and a.shape == (op.nnz, ) and a.is_contiguous() and a.is_cuda
-        lib = _lib.load()
-        C = torch.empty(op.n_rows, dtype=torch.float32, device=dval.device)
-        ws = self._edge_ws("colsum", lib.glass_adj_colsum_ws_bytes(op.header.ctypes.data))
-        rc = lib.glass_adj_colsum_f32(op.rowptr.data_ptr(), op.col.data_ptr(), val_t.data_ptr(), eid_t.data_ptr(), dval.data_ptr(),
-                                      C.data_ptr(), op.n_rows, op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
-                                      torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_adj_colsum_f32")
+        C = _empty(dval, op.n_rows)
+        _launch(op, cache, "colsum", "glass_adj_colsum_f32", "glass_adj_colsum_ws_bytes", (dval.data_ptr(), C.data_ptr()),
+                eid_t=eid_t, val=val_t)
         return C
 
     def values_bwd(self, dval, R, C, w, deg=None):
@@ -316,13 +348,10 @@ class CSRAdj:
         assert dval.dtype == torch.float32 and dval.shape == (op.nnz, ) and dval.is_contiguous() and dval.is_cuda
         for a in (R, C, deg):
             assert a is None or (a.dtype == torch.float32 and a.shape == (self.n_node, ) and a.is_contiguous() and a.is_cuda)
-        dw = torch.empty(op.nnz, dtype=torch.float32, device=dval.device)
+        dw = _empty(dval, op.nnz)
         ptr = lambda a: None if a is None else a.data_ptr()
-        rc = _lib.load().glass_adj_values_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), perm32.data_ptr(), ptr(deg),
-                                                  dval.data_ptr(), ptr(R), ptr(C), self.n_node, op.nnz,
-                                                  _lib.AGGR_MODES[self.aggr], dw.data_ptr(),
-                                                  torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_adj_values_bwd_f32")
+        _run("glass_adj_values_bwd_f32", (op.rowptr.data_ptr(), op.col.data_ptr(), perm32.data_ptr(), ptr(deg), dval.data_ptr(),
+                                          ptr(R), ptr(C), self.n_node, op.nnz, _lib.AGGR_MODES[self.aggr], dw.data_ptr()))
         return dw
 
     # ---- K2d: edge dropout (aggr "sum", "mean", "gcn"; csrc/spmm_dropedge.hip) -------------------------------------------------
@@ -373,13 +402,11 @@ class CSRAdj:
                 from . import ops
                 rng = ops.rng_tensor(dev)
             assert rng.dtype == torch.int64 and rng.numel() == 2 and rng.device == dev
-            rc = _lib.load().glass_adj_dropedge_f32(op.rowptr.data_ptr(), op.col.data_ptr(), w.data_ptr(), self.bwd.rowptr.data_ptr(),
-                                                    self.bwd.col.data_ptr(), w_t.data_ptr(), self.n_node, _lib.AGGR_MODES[self.aggr],
-                                                    p, 1 if symmetric else 0, rng.data_ptr(), int(call_id), b["deg"].data_ptr(),
-                                                    b["val"].data_ptr(), b["val_t"].data_ptr(),
-                                                    b["keep"].data_ptr() if want_keep else None,
-                                                    torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, "glass_adj_dropedge_f32")
+            _run("glass_adj_dropedge_f32", (op.rowptr.data_ptr(), op.col.data_ptr(), w.data_ptr(), self.bwd.rowptr.data_ptr(),
+                                            self.bwd.col.data_ptr(), w_t.data_ptr(), self.n_node, _lib.AGGR_MODES[self.aggr], p,
+                                            1 if symmetric else 0, rng.data_ptr(), int(call_id), b["deg"].data_ptr(),
+                                            b["val"].data_ptr(), b["val_t"].data_ptr(),
+                                            b["keep"].data_ptr() if want_keep else None))
         out = (b["val"], b["val_t"], b["deg"])
         return out + (b["keep"], ) if want_keep else out
 
@@ -388,58 +415,34 @@ class CSRAdj:
         so far — a holder of the tensors knows from it whether they still hold ITS draw."""
         return self._dropedge_state("dropedge_record")[2][(int(call_id), _ws_branch)]
 
-    def _need_max(self, what):
-        if self.aggr != "max":
-            raise _lib.GlassHipError(f"CSRAdj.{what}: this adjacency was built for aggr {self.aggr!r}, not 'max'")
-
+    # ---- K1m: aggr "max" (csrc/spmm_max.hip) -------------------------------------------------------------------------------
     def max_fwd(self, x):
         """(y, arg) = K1m forward: y[i, c] = max over the entries e of row i of val[e] * x[col[e], c], arg the winning e
         (int32; -1 and y = 0 for a row without entries)."""
-        self._need_max("max_fwd")
+        self._need("max_fwd", "max")
         op = self.fwd
-        assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32 and x.is_cuda
-        assert x.shape[0] == op.n_cols, f"X has {x.shape[0]} rows, matrix has {op.n_cols} columns"
+        ldx = _operand(x, op.n_cols, "X")
         H = x.shape[1]
-        lib = _lib.load()
-        y = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
-        arg = torch.empty((op.n_rows, H), dtype=torch.int32, device=x.device)
-        ws = self._aggr_workspace("max_fwd", H, lib.glass_spmm_max_ws_bytes(op.header.ctypes.data, H))
-        ldx = x.stride(0) if x.shape[0] > 1 else max(H, x.stride(0))
-        rc = lib.glass_spmm_max_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
-                                        y.data_ptr(), H, arg.data_ptr(), H, op.n_rows, H, op.header.ctypes.data,
-                                        op.plan.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_max_csr_f32")
+        y = _empty(x, op.n_rows, H)
+        arg = _empty(x, op.n_rows, H, dtype=torch.int32)
+        _launch(op, self._aggr_ws, "max_fwd", "glass_spmm_max_csr_f32", "glass_spmm_max_ws_bytes",
+                (x.data_ptr(), ldx, y.data_ptr(), H, arg.data_ptr(), H), H)
         return y, arg
 
     def max_bwd(self, dy, arg):
         """dx of K1m: every dy[i, c] goes, times its entry's weight, to the source of the entry arg[i, c] names."""
-        self._need_max("max_bwd")
+        self._need("max_bwd", "max")
         op = self.bwd
-        assert dy.dim() == 2 and dy.stride(1) == 1 and dy.dtype == torch.float32 and dy.is_cuda
-        assert arg.dtype == torch.int32 and arg.shape == dy.shape and arg.stride(1) == 1 and dy.shape[0] == op.n_cols
+        ldy = _operand(dy, op.n_cols, "dY")
+        lda = _operand(arg, op.n_cols, "arg", torch.int32)
+        assert arg.shape == dy.shape
         H = dy.shape[1]
-        lib = _lib.load()
-        dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=dy.device)
-        ws = self._aggr_workspace("max_bwd", H, lib.glass_spmm_max_bwd_ws_bytes(op.header.ctypes.data, H))
-        ldy = dy.stride(0) if dy.shape[0] > 1 else max(H, dy.stride(0))
-        lda = arg.stride(0) if arg.shape[0] > 1 else max(H, arg.stride(0))
-        rc = lib.glass_spmm_max_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
-                                        dy.data_ptr(), ldy, arg.data_ptr(), lda, dx.data_ptr(), H, op.n_rows, H,
-                                        op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
-                                        torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_max_bwd_f32")
+        dx = _empty(dy, op.n_rows, H)
+        _launch(op, self._aggr_ws, "max_bwd", "glass_spmm_max_bwd_f32", "glass_spmm_max_bwd_ws_bytes",
+                (dy.data_ptr(), ldy, arg.data_ptr(), lda, dx.data_ptr(), H), H, eid_t=self.eid_t)
         return dx
 
-    def _need_softmax(self, what):
-        if self.aggr != "softmax":
-            raise _lib.GlassHipError(f"CSRAdj.{what}: this adjacency was built for aggr {self.aggr!r}, not 'softmax'")
-
-    @staticmethod
-    def _softmax_operand(a, n, name):
-        assert a.dim() == 2 and a.stride(1) == 1 and a.dtype == torch.float32 and a.is_cuda, name
-        assert a.shape[0] == n, f"{name} has {a.shape[0]} rows, the adjacency has {n} nodes"
-        return a.stride(0) if a.shape[0] > 1 else max(a.shape[1], a.stride(0))
-
+    # ---- K1s: aggr "softmax" (csrc/spmm_softmax.hip) -------------------------------------------------------------------------
     @staticmethod
     def _softmax_t(t, like):
         assert t.numel() == 1 and t.dtype == torch.float32 and t.device == like.device, "t: one fp32 on the operand's device"
@@ -448,127 +451,95 @@ class CSRAdj:
     def softmax_fwd(self, x, t):
         """(y, lse) = K1s forward: per destination and channel the softmax-weighted mean of the neighbour messages at temperature
         t (one fp32 on the device), lse = max + log of the weighted sum of exponentials, kept for the backward."""
-        self._need_softmax("softmax_fwd")
+        self._need("softmax_fwd", "softmax")
         op = self.fwd
-        ldx = self._softmax_operand(x, op.n_cols, "X")
+        ldx = _operand(x, op.n_cols, "X")
         H = x.shape[1]
-        lib = _lib.load()
-        y = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
-        lse = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
-        ws = self._aggr_workspace("softmax_fwd", H, lib.glass_spmm_softmax_ws_bytes(op.header.ctypes.data, H))
-        rc = lib.glass_spmm_softmax_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
-                                            self._softmax_t(t, x), y.data_ptr(), H, lse.data_ptr(), H, op.n_rows, H,
-                                            op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
-                                            torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_softmax_csr_f32")
+        y = _empty(x, op.n_rows, H)
+        lse = _empty(x, op.n_rows, H)
+        _launch(op, self._aggr_ws, "softmax_fwd", "glass_spmm_softmax_csr_f32", "glass_spmm_softmax_ws_bytes",
+                (x.data_ptr(), ldx, self._softmax_t(t, x), y.data_ptr(), H, lse.data_ptr(), H), H)
         return y, lse
 
     def softmax_bwd(self, dy, x, y, lse, t):
         """dx of K1s, from the forward's operand x and its results (y, lse)."""
-        self._need_softmax("softmax_bwd")
+        self._need("softmax_bwd", "softmax")
         op = self.bwd
-        ldx = self._softmax_operand(x, op.n_rows, "X")
-        lddy, ldy, ldl = (self._softmax_operand(a, op.n_cols, n) for a, n in ((dy, "dY"), (y, "Y"), (lse, "L")))
+        ldx = _operand(x, op.n_rows, "X")
+        lddy, ldy, ldl = (_operand(a, op.n_cols, n) for a, n in ((dy, "dY"), (y, "Y"), (lse, "L")))
         assert dy.shape == x.shape == y.shape == lse.shape
         H = x.shape[1]
-        lib = _lib.load()
-        dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
-        ws = self._aggr_workspace("softmax_bwd", H, lib.glass_spmm_softmax_bwd_ws_bytes(op.header.ctypes.data, H))
-        rc = lib.glass_spmm_softmax_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
-                                            self._softmax_t(t, x), dy.data_ptr(), lddy, y.data_ptr(), ldy, lse.data_ptr(), ldl,
-                                            dx.data_ptr(), H, op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
-                                            ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_softmax_bwd_f32")
+        dx = _empty(x, op.n_rows, H)
+        _launch(op, self._aggr_ws, "softmax_bwd", "glass_spmm_softmax_bwd_f32", "glass_spmm_softmax_bwd_ws_bytes",
+                (x.data_ptr(), ldx, self._softmax_t(t, x), dy.data_ptr(), lddy, y.data_ptr(), ldy, lse.data_ptr(), ldl,
+                 dx.data_ptr(), H), H)
         return dx
 
     def softmax_dt(self, dy, x, y, lse, t):
         """The temperature's gradient (shape [1]): a further pass over the forward CSR, run only when t is trained."""
-        self._need_softmax("softmax_dt")
+        self._need("softmax_dt", "softmax")
         op = self.fwd
-        ldx = self._softmax_operand(x, op.n_cols, "X")
-        lddy, ldy, ldl = (self._softmax_operand(a, op.n_rows, n) for a, n in ((dy, "dY"), (y, "Y"), (lse, "L")))
+        ldx = _operand(x, op.n_cols, "X")
+        lddy, ldy, ldl = (_operand(a, op.n_rows, n) for a, n in ((dy, "dY"), (y, "Y"), (lse, "L")))
         assert dy.shape == x.shape == y.shape == lse.shape
         H = x.shape[1]
-        lib = _lib.load()
         dt = torch.zeros(1, dtype=torch.float32, device=x.device)
-        ws = self._aggr_workspace("softmax_dt", H, lib.glass_spmm_softmax_dt_ws_bytes(op.header.ctypes.data, H))
-        rc = lib.glass_spmm_softmax_dt_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
-                                           self._softmax_t(t, x), dy.data_ptr(), lddy, y.data_ptr(), ldy, lse.data_ptr(), ldl,
-                                           dt.data_ptr(), op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
-                                           ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_softmax_dt_f32")
+        _launch(op, self._aggr_ws, "softmax_dt", "glass_spmm_softmax_dt_f32", "glass_spmm_softmax_dt_ws_bytes",
+                (x.data_ptr(), ldx, self._softmax_t(t, x), dy.data_ptr(), lddy, y.data_ptr(), ldy, lse.data_ptr(), ldl,
+                 dt.data_ptr()), H)
         return dt
 
-    def _need_moment(self, what):
-        if self.aggr not in MOMENT_KINDS:
-            raise _lib.GlassHipError(f"CSRAdj.{what}: this adjacency was built for aggr {self.aggr!r}, not 'std' or 'var'")
-
+    # ---- K1v: aggr "std" / "var" (csrc/spmm_moment.hip) ----------------------------------------------------------------------
     def moment_fwd(self, x, kind=None, eps=1e-5):
         """(s, mu, wsum) = K1v forward: per destination and channel the weighted standard deviation sqrt(var + eps) (kind "std")
         or variance (kind "var"; None: the adjacency's own aggr) of the neighbour messages, their weighted mean, and per
         destination the sum of its weights; zeros for a row without entries."""
-        self._need_moment("moment_fwd")
+        self._need("moment_fwd", *MOMENT_KINDS)
         kind = self.aggr if kind is None else kind
         if kind not in MOMENT_KINDS:
             raise ValueError(f"moment_fwd: kind must be 'std' or 'var', not {kind!r}")
         op = self.fwd
-        ldx = self._softmax_operand(x, op.n_cols, "X")
+        ldx = _operand(x, op.n_cols, "X")
         H = x.shape[1]
-        lib = _lib.load()
-        s = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
-        mu = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
-        wsum = torch.empty(op.n_rows, dtype=torch.float32, device=x.device)
-        ws = self._aggr_workspace("moment_fwd", H, lib.glass_spmm_moment_ws_bytes(op.header.ctypes.data, H))
-        rc = lib.glass_spmm_moment_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
-                                           float(eps), MOMENT_KINDS[kind], s.data_ptr(), H, mu.data_ptr(), H, wsum.data_ptr(),
-                                           op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
-                                           torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_moment_csr_f32")
+        s = _empty(x, op.n_rows, H)
+        mu = _empty(x, op.n_rows, H)
+        wsum = _empty(x, op.n_rows)
+        _launch(op, self._aggr_ws, "moment_fwd", "glass_spmm_moment_csr_f32", "glass_spmm_moment_ws_bytes",
+                (x.data_ptr(), ldx, float(eps), MOMENT_KINDS[kind], s.data_ptr(), H, mu.data_ptr(), H, wsum.data_ptr()), H)
         return s, mu, wsum
 
     def moment_bwd(self, x, mu, A, C=None):
         """dx of K1v from the forward's operand x, its mean mu and the caller's per-destination factors A and C (None: the mean
         carries no gradient): dx[j] = sum over the entries (destination i) of val * (C[i] + A[i] * (x[j] - mu[i]))."""
-        self._need_moment("moment_bwd")
+        self._need("moment_bwd", *MOMENT_KINDS)
         op = self.bwd
-        ldx = self._softmax_operand(x, op.n_rows, "X")
-        ldmu, lda = (self._softmax_operand(a, op.n_cols, n) for a, n in ((mu, "Mu"), (A, "A")))
-        ldc = 0 if C is None else self._softmax_operand(C, op.n_cols, "C")
+        ldx = _operand(x, op.n_rows, "X")
+        ldmu, lda = (_operand(a, op.n_cols, n) for a, n in ((mu, "Mu"), (A, "A")))
+        ldc = 0 if C is None else _operand(C, op.n_cols, "C")
         assert x.shape == mu.shape == A.shape and (C is None or C.shape == x.shape)
         H = x.shape[1]
-        lib = _lib.load()
-        dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
-        ws = self._aggr_workspace("moment_bwd", H, lib.glass_spmm_moment_bwd_ws_bytes(op.header.ctypes.data, H))
-        rc = lib.glass_spmm_moment_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
-                                           mu.data_ptr(), ldmu, A.data_ptr(), lda, None if C is None else C.data_ptr(), ldc,
-                                           dx.data_ptr(), H, op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
-                                           ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_moment_bwd_f32")
+        dx = _empty(x, op.n_rows, H)
+        _launch(op, self._aggr_ws, "moment_bwd", "glass_spmm_moment_bwd_f32", "glass_spmm_moment_bwd_ws_bytes",
+                (x.data_ptr(), ldx, mu.data_ptr(), ldmu, A.data_ptr(), lda, None if C is None else C.data_ptr(), ldc,
+                 dx.data_ptr(), H), H)
         return dx
 
-    def _need_pna(self, what):
-        if self.aggr != "pna":
-            raise _lib.GlassHipError(f"CSRAdj.{what}: this adjacency was built for aggr {self.aggr!r}, not 'pna'")
-
+    # ---- K1p: aggr "pna" (csrc/spmm_pna.hip) ---------------------------------------------------------------------------------
     def pna_fwd(self, x, eps=1e-5):
         """(mu, s, mx, mn, amx, amn, wsum) = K1p forward, one gather of every source row: per destination and channel the
         weighted mean and standard deviation sqrt(var + eps) of the neighbour messages, their largest and smallest with the
         winning entries (int32, -1 for a row without entries), and per destination the sum of its weights; zeros for a row
         without entries."""
-        self._need_pna("pna_fwd")
+        self._need("pna_fwd", "pna")
         op = self.fwd
-        ldx = self._softmax_operand(x, op.n_cols, "X")
+        ldx = _operand(x, op.n_cols, "X")
         H = x.shape[1]
-        lib = _lib.load()
-        mu, s, mx, mn = (torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device) for _ in range(4))
-        amx, amn = (torch.empty((op.n_rows, H), dtype=torch.int32, device=x.device) for _ in range(2))
-        wsum = torch.empty(op.n_rows, dtype=torch.float32, device=x.device)
-        ws = self._aggr_workspace("pna_fwd", H, lib.glass_spmm_pna_ws_bytes(op.header.ctypes.data, H))
-        rc = lib.glass_spmm_pna_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx, float(eps),
-                                        mu.data_ptr(), H, s.data_ptr(), H, mx.data_ptr(), H, mn.data_ptr(), H, amx.data_ptr(), H,
-                                        amn.data_ptr(), H, wsum.data_ptr(), op.n_rows, H, op.header.ctypes.data,
-                                        op.plan.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_pna_csr_f32")
+        mu, s, mx, mn = (_empty(x, op.n_rows, H) for _ in range(4))
+        amx, amn = (_empty(x, op.n_rows, H, dtype=torch.int32) for _ in range(2))
+        wsum = _empty(x, op.n_rows)
+        _launch(op, self._aggr_ws, "pna_fwd", "glass_spmm_pna_csr_f32", "glass_spmm_pna_ws_bytes",
+                (x.data_ptr(), ldx, float(eps), mu.data_ptr(), H, s.data_ptr(), H, mx.data_ptr(), H, mn.data_ptr(), H,
+                 amx.data_ptr(), H, amn.data_ptr(), H, wsum.data_ptr()), H)
         return mu, s, mx, mn, amx, amn, wsum
 
     def pna_bwd(self, x, mu, A, C, amx, gmx, amn, gmn):
@@ -576,31 +547,21 @@ class CSRAdj:
         (ops.pna_factors), gmx and gmn (all required: zeros for a result without a gradient):
         dx[j] = sum over the entries (destination i) of val * (C[i] + A[i] * (x[j] - mu[i])) + gmx[i] where this entry won
         the max + gmn[i] where it won the min."""
-        self._need_pna("pna_bwd")
+        self._need("pna_bwd", "pna")
         op = self.bwd
-        ldx = self._softmax_operand(x, op.n_rows, "X")
-        ldmu, lda, ldc, ldgx, ldgn = (self._softmax_operand(a, op.n_cols, n)
+        ldx = _operand(x, op.n_rows, "X")
+        ldmu, lda, ldc, ldgx, ldgn = (_operand(a, op.n_cols, n)
                                       for a, n in ((mu, "Mu"), (A, "A"), (C, "C"), (gmx, "Gmx"), (gmn, "Gmn")))
-        for a in (amx, amn):
-            assert a.dtype == torch.int32 and a.dim() == 2 and a.stride(1) == 1 and a.is_cuda and a.shape == x.shape
-        assert x.shape == mu.shape == A.shape == C.shape == gmx.shape == gmn.shape
+        ldax, ldan = (_operand(a, op.n_cols, n, torch.int32) for a, n in ((amx, "Amx"), (amn, "Amn")))
+        assert x.shape == mu.shape == A.shape == C.shape == gmx.shape == gmn.shape == amx.shape == amn.shape
         H = x.shape[1]
-        ldax, ldan = (a.stride(0) if a.shape[0] > 1 else max(H, a.stride(0)) for a in (amx, amn))
-        lib = _lib.load()
-        dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
-        ws = self._aggr_workspace("pna_bwd", H, lib.glass_spmm_pna_bwd_ws_bytes(op.header.ctypes.data, H))
-        rc = lib.glass_spmm_pna_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
-                                        x.data_ptr(), ldx, mu.data_ptr(), ldmu, A.data_ptr(), lda, C.data_ptr(), ldc,
-                                        amx.data_ptr(), ldax, gmx.data_ptr(), ldgx, amn.data_ptr(), ldan, gmn.data_ptr(), ldgn,
-                                        dx.data_ptr(), H, op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
-                                        ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_pna_bwd_f32")
+        dx = _empty(x, op.n_rows, H)
+        _launch(op, self._aggr_ws, "pna_bwd", "glass_spmm_pna_bwd_f32", "glass_spmm_pna_bwd_ws_bytes",
+                (x.data_ptr(), ldx, mu.data_ptr(), ldmu, A.data_ptr(), lda, C.data_ptr(), ldc, amx.data_ptr(), ldax,
+                 gmx.data_ptr(), ldgx, amn.data_ptr(), ldan, gmn.data_ptr(), ldgn, dx.data_ptr(), H), H, eid_t=self.eid_t)
         return dx
 
-    def _need_gat(self, what):
-        if self.aggr != "gat":
-            raise _lib.GlassHipError(f"CSRAdj.{what}: this adjacency was built for aggr {self.aggr!r}, not 'gat'")
-
+    # ---- K1a: aggr "gat" (csrc/spmm_gat.hip; heads = K > 1: the glass_*_mh_* entries, csrc/spmm_gat_mh.hip) ------------------
     def _gat_vec(self, v, n, name):
         assert v.dim() == 1 and v.shape[0] == n and v.stride(0) == 1 and v.dtype == torch.float32 and v.is_cuda, \
             f"{name}: {n} contiguous fp32 on the device"
@@ -627,184 +588,107 @@ class CSRAdj:
             f"{name}: [{n}, {K}] contiguous fp32 on the device"
         return v.data_ptr()
 
+    def _gat_form(self, H, heads):
+        """(kdim, mh, tmp) of one gat call.  heads == 1 is ALWAYS the single-head entries — other kernels, with other bits, than
+        glass_*_mh_* at K = 1, and they take any width: kdim (), mh "", the per-node temporaries [n], checked by
+        tmp(v, n, name).  heads = K > 1: (K, ) — what follows H among the arguments and n in the temporaries' shapes [n, K] —
+        and "_mh", the infix of the entries' names; a width the heads do not cut into powers of two raises here, before any
+        launch."""
+        if heads == 1:
+            return (), "", self._gat_vec
+        K = int(heads)
+        self.gat_head_width(H, K)
+        return (K, ), "_mh", lambda v, n, name: self._gat_mat(v, n, K, name)
+
     def gat_scores(self, x, att_src, att_dst, heads=1):
         """(a, b) = K1a node scores: a = x @ att_src, b = x @ att_dst, [N] each (fp64 sums, rounded once).  heads = K > 1: per
-        head, over the head's columns, [N, K] each (here and below: the glass_*_mh_* entries, csrc/spmm_gat_mh.hip)."""
-        self._need_gat("gat_scores")
-        ldx = self._softmax_operand(x, self.n_node, "X")
+        head, over the head's columns, [N, K] each."""
+        self._need("gat_scores", "gat")
+        ldx = _operand(x, self.n_node, "X")
         H = x.shape[1]
-        if heads != 1:
-            K = int(heads)
-            self.gat_head_width(H, K)
-            a = torch.empty((self.n_node, K), dtype=torch.float32, device=x.device)
-            b = torch.empty((self.n_node, K), dtype=torch.float32, device=x.device)
-            rc = _lib.load().glass_gat_scores_mh_f32(x.data_ptr(), ldx, self._gat_vec(att_src, H, "att_src"),
-                                                     self._gat_vec(att_dst, H, "att_dst"), a.data_ptr(), b.data_ptr(), self.n_node,
-                                                     H, K, torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, "glass_gat_scores_mh_f32")
-            return a, b
-        a = torch.empty(self.n_node, dtype=torch.float32, device=x.device)
-        b = torch.empty(self.n_node, dtype=torch.float32, device=x.device)
-        rc = _lib.load().glass_gat_scores_f32(x.data_ptr(), ldx, self._gat_vec(att_src, H, "att_src"),
-                                              self._gat_vec(att_dst, H, "att_dst"), a.data_ptr(), b.data_ptr(), self.n_node, H,
-                                              torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_gat_scores_f32")
+        kdim, mh, _tmp = self._gat_form(H, heads)
+        a = _empty(x, self.n_node, *kdim)
+        b = _empty(x, self.n_node, *kdim)
+        _run(f"glass_gat_scores{mh}_f32", (x.data_ptr(), ldx, self._gat_vec(att_src, H, "att_src"),
+                                           self._gat_vec(att_dst, H, "att_dst"), a.data_ptr(), b.data_ptr(), self.n_node, H, *kdim))
         return a, b
 
     def gat_fwd(self, x, a, b, slope, heads=1):
         """(y, lse) = K1a forward: per destination the attention-weighted mean of the neighbour messages, the weights a softmax
-        over the row's entries of LeakyReLU(a[source] + b[destination]); lse [N] = max + log of the weighted sum of
+        over the row's entries of LeakyReLU(a[source] + b[destination]); lse [N] ([N, K]) = max + log of the weighted sum of
         exponentials, kept for the backward."""
-        self._need_gat("gat_fwd")
+        self._need("gat_fwd", "gat")
         op = self.fwd
-        ldx = self._softmax_operand(x, op.n_cols, "X")
+        ldx = _operand(x, op.n_cols, "X")
         H = x.shape[1]
-        lib = _lib.load()
-        y = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
-        if heads != 1:  # lse [N, K]
-            K = int(heads)
-            self.gat_head_width(H, K)
-            lse = torch.empty((op.n_rows, K), dtype=torch.float32, device=x.device)
-            ws = self._aggr_workspace("gat_fwd", (H, K), lib.glass_spmm_gat_mh_ws_bytes(op.header.ctypes.data, H, K))
-            rc = lib.glass_spmm_gat_mh_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
-                                               self._gat_mat(a, op.n_cols, K, "a"), self._gat_mat(b, op.n_rows, K, "b"),
-                                               float(slope), y.data_ptr(), H, lse.data_ptr(), op.n_rows, H, K,
-                                               op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
-                                               torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, "glass_spmm_gat_mh_csr_f32")
-            return y, lse
-        lse = torch.empty(op.n_rows, dtype=torch.float32, device=x.device)
-        ws = self._aggr_workspace("gat_fwd", H, lib.glass_spmm_gat_ws_bytes(op.header.ctypes.data, H))
-        rc = lib.glass_spmm_gat_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
-                                        self._gat_vec(a, op.n_cols, "a"), self._gat_vec(b, op.n_rows, "b"), float(slope),
-                                        y.data_ptr(), H, lse.data_ptr(), op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(),
-                                        ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_gat_csr_f32")
+        kdim, mh, tmp = self._gat_form(H, heads)
+        y = _empty(x, op.n_rows, H)
+        lse = _empty(x, op.n_rows, *kdim)
+        _launch(op, self._aggr_ws, "gat_fwd", f"glass_spmm_gat{mh}_csr_f32", f"glass_spmm_gat{mh}_ws_bytes",
+                (x.data_ptr(), ldx, tmp(a, op.n_cols, "a"), tmp(b, op.n_rows, "b"), float(slope), y.data_ptr(), H, lse.data_ptr()),
+                H, *kdim)
         return y, lse
 
     def gat_edge(self, dy, x, y, lse, a, b, slope, heads=1):
-        """(g, db) = K1a edge pass over the forward CSR: g [nnz] the score gradient of every entry, in forward entry order (a
-        sampled dense-dense product: per entry the dot of dy[destination] and x[source]), db [N] its row sums."""
-        self._need_gat("gat_edge")
+        """(g, db) = K1a edge pass over the forward CSR: g [nnz] ([nnz, K]) the score gradient of every entry, in forward entry
+        order (a sampled dense-dense product: per entry the dot of dy[destination] and x[source]), db [N] ([N, K]) its row sums."""
+        self._need("gat_edge", "gat")
         op = self.fwd
-        ldx = self._softmax_operand(x, op.n_cols, "X")
-        lddy, ldy = (self._softmax_operand(t, op.n_rows, n) for t, n in ((dy, "dY"), (y, "Y")))
+        ldx = _operand(x, op.n_cols, "X")
+        lddy, ldy = (_operand(t, op.n_rows, n) for t, n in ((dy, "dY"), (y, "Y")))
         assert dy.shape == x.shape == y.shape
         H = x.shape[1]
-        lib = _lib.load()
-        if heads != 1:  # g [nnz, K], db [N, K]
-            K = int(heads)
-            self.gat_head_width(H, K)
-            g = torch.empty((max(op.nnz, 1), K), dtype=torch.float32, device=x.device)[:op.nnz]
-            db = torch.empty((op.n_rows, K), dtype=torch.float32, device=x.device)
-            ws = self._aggr_workspace("gat_edge", (H, K), lib.glass_spmm_gat_mh_edge_ws_bytes(op.header.ctypes.data, H, K))
-            rc = lib.glass_spmm_gat_mh_edge_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
-                                                self._gat_mat(a, op.n_cols, K, "a"), self._gat_mat(b, op.n_rows, K, "b"),
-                                                float(slope), dy.data_ptr(), lddy, y.data_ptr(), ldy,
-                                                self._gat_mat(lse, op.n_rows, K, "L"), g.data_ptr(), db.data_ptr(), op.n_rows, H, K,
-                                                op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
-                                                torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, "glass_spmm_gat_mh_edge_f32")
-            return g, db
-        g = torch.empty(max(op.nnz, 1), dtype=torch.float32, device=x.device)[:op.nnz]
-        db = torch.empty(op.n_rows, dtype=torch.float32, device=x.device)
-        ws = self._aggr_workspace("gat_edge", H, lib.glass_spmm_gat_edge_ws_bytes(op.header.ctypes.data, H))
-        rc = lib.glass_spmm_gat_edge_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(), ldx,
-                                         self._gat_vec(a, op.n_cols, "a"), self._gat_vec(b, op.n_rows, "b"), float(slope),
-                                         dy.data_ptr(), lddy, y.data_ptr(), ldy, self._gat_vec(lse, op.n_rows, "L"), g.data_ptr(),
-                                         db.data_ptr(), op.n_rows, H, op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
-                                         torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_gat_edge_f32")
+        kdim, mh, tmp = self._gat_form(H, heads)
+        g = _empty(x, max(op.nnz, 1), *kdim)[:op.nnz]
+        db = _empty(x, op.n_rows, *kdim)
+        _launch(op, self._aggr_ws, "gat_edge", f"glass_spmm_gat{mh}_edge_f32", f"glass_spmm_gat{mh}_edge_ws_bytes",
+                (x.data_ptr(), ldx, tmp(a, op.n_cols, "a"), tmp(b, op.n_rows, "b"), float(slope), dy.data_ptr(), lddy, y.data_ptr(),
+                 ldy, tmp(lse, op.n_rows, "L"), g.data_ptr(), db.data_ptr()), H, *kdim)
         return g, db
 
     def gat_bwd(self, dy, lse, a, b, g, db, att_src, att_dst, slope, heads=1):
         """(dx, da) = K1a transposed pass: dx[j] = the attention-weighted sum of dy over the entries that read x[j], plus
-        da[j] att_src + db[j] att_dst; da [N] = the sums of g over those entries."""
-        self._need_gat("gat_bwd")
+        da[j] att_src + db[j] att_dst; da [N] ([N, K]) = the sums of g over those entries."""
+        self._need("gat_bwd", "gat")
         op = self.bwd
-        lddy = self._softmax_operand(dy, op.n_cols, "dY")
+        lddy = _operand(dy, op.n_cols, "dY")
         H = dy.shape[1]
-        lib = _lib.load()
-        dx = torch.empty((op.n_rows, H), dtype=torch.float32, device=dy.device)
-        if heads != 1:  # da [N, K]
-            K = int(heads)
-            self.gat_head_width(H, K)
-            da = torch.empty((op.n_rows, K), dtype=torch.float32, device=dy.device)
-            ws = self._aggr_workspace("gat_bwd", (H, K), lib.glass_spmm_gat_mh_bwd_ws_bytes(op.header.ctypes.data, H, K))
-            rc = lib.glass_spmm_gat_mh_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
-                                               self._gat_mat(a, op.n_rows, K, "a"), self._gat_mat(b, op.n_cols, K, "b"),
-                                               float(slope), dy.data_ptr(), lddy, self._gat_mat(lse, op.n_cols, K, "L"),
-                                               self._gat_mat(g, op.nnz, K, "g"), self._gat_mat(db, op.n_rows, K, "db"),
-                                               self._gat_vec(att_src, H, "att_src"), self._gat_vec(att_dst, H, "att_dst"),
-                                               dx.data_ptr(), H, da.data_ptr(), op.n_rows, H, K, op.header.ctypes.data,
-                                               op.plan.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, "glass_spmm_gat_mh_bwd_f32")
-            return dx, da
-        da = torch.empty(op.n_rows, dtype=torch.float32, device=dy.device)
-        assert g.dtype == torch.float32 and g.shape == (op.nnz, ) and g.stride(0) == 1
-        ws = self._aggr_workspace("gat_bwd", H, lib.glass_spmm_gat_bwd_ws_bytes(op.header.ctypes.data, H))
-        rc = lib.glass_spmm_gat_bwd_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
-                                        self._gat_vec(a, op.n_rows, "a"), self._gat_vec(b, op.n_cols, "b"), float(slope),
-                                        dy.data_ptr(), lddy, self._gat_vec(lse, op.n_cols, "L"), g.data_ptr(),
-                                        self._gat_vec(db, op.n_rows, "db"), self._gat_vec(att_src, H, "att_src"),
-                                        self._gat_vec(att_dst, H, "att_dst"), dx.data_ptr(), H, da.data_ptr(), op.n_rows, H,
-                                        op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
-                                        torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_gat_bwd_f32")
+        kdim, mh, tmp = self._gat_form(H, heads)
+        dx = _empty(dy, op.n_rows, H)
+        da = _empty(dy, op.n_rows, *kdim)
+        _launch(op, self._aggr_ws, "gat_bwd", f"glass_spmm_gat{mh}_bwd_f32", f"glass_spmm_gat{mh}_bwd_ws_bytes",
+                (tmp(a, op.n_rows, "a"), tmp(b, op.n_cols, "b"), float(slope), dy.data_ptr(), lddy, tmp(lse, op.n_cols, "L"),
+                 tmp(g, op.nnz, "g"), tmp(db, op.n_rows, "db"), self._gat_vec(att_src, H, "att_src"),
+                 self._gat_vec(att_dst, H, "att_dst"), dx.data_ptr(), H, da.data_ptr()), H, *kdim, eid_t=self.eid_t)
         return dx, da
 
     def gat_da(self, g, dy, heads=1):
         """da alone (gat_bwd's second result, the same bits) when no dx is wanted; dy only names the lane layout gat_bwd would
         take (its width, stride and alignment)."""
-        self._need_gat("gat_da")
+        self._need("gat_da", "gat")
         op = self.bwd
-        lddy = self._softmax_operand(dy, op.n_cols, "dY")
+        lddy = _operand(dy, op.n_cols, "dY")
         H = dy.shape[1]
-        lib = _lib.load()
-        if heads != 1:
-            K = int(heads)
-            self.gat_head_width(H, K)
-            da = torch.empty((op.n_rows, K), dtype=torch.float32, device=g.device)
-            ws = self._aggr_workspace("gat_da", (H, K), lib.glass_spmm_gat_mh_da_ws_bytes(op.header.ctypes.data, H, K))
-            vec = lddy % 4 == 0 and dy.data_ptr() % 16 == 0  # (gat_bwd's own dx and workspace are 16-byte aligned)
-            rc = lib.glass_spmm_gat_mh_da_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
-                                              self._gat_mat(g, op.nnz, K, "g"), da.data_ptr(), op.n_rows, H, K, int(vec),
-                                              op.header.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
-                                              torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, "glass_spmm_gat_mh_da_f32")
-            return da
-        da = torch.empty(op.n_rows, dtype=torch.float32, device=g.device)
-        assert g.dtype == torch.float32 and g.shape == (op.nnz, ) and g.stride(0) == 1
-        ws = self._aggr_workspace("gat_da", H, lib.glass_spmm_gat_da_ws_bytes(op.header.ctypes.data, H))
-        vec = H % 4 == 0 and lddy % 4 == 0 and dy.data_ptr() % 16 == 0  # (gat_bwd's own dx and workspace are 16-byte aligned)
-        rc = lib.glass_spmm_gat_da_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), self.eid_t.data_ptr(),
-                                       g.data_ptr(), da.data_ptr(), op.n_rows, H, int(vec), op.header.ctypes.data,
-                                       op.plan.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_gat_da_f32")
+        kdim, mh, tmp = self._gat_form(H, heads)
+        da = _empty(g, op.n_rows, *kdim)
+        # gat_bwd's 16-byte form (its own dx and workspace are 16-byte aligned); several heads have H % 4 == 0 by their width
+        vec = H % 4 == 0 and lddy % 4 == 0 and dy.data_ptr() % 16 == 0
+        _launch(op, self._aggr_ws, "gat_da", f"glass_spmm_gat{mh}_da_f32", f"glass_spmm_gat{mh}_da_ws_bytes",
+                (tmp(g, op.nnz, "g"), da.data_ptr()), H, *kdim, eid_t=self.eid_t, tail=(int(vec), ))
         return da
 
     def gat_datt(self, x, da, db, heads=1):
         """(datt_src, datt_dst) = x^T da, x^T db: the attention vectors' gradients, run only when they are trained."""
-        self._need_gat("gat_datt")
-        ldx = self._softmax_operand(x, self.n_node, "X")
+        self._need("gat_datt", "gat")
+        ldx = _operand(x, self.n_node, "X")
         H = x.shape[1]
-        lib = _lib.load()
+        kdim, mh, tmp = self._gat_form(H, heads)
         ds = torch.zeros(H, dtype=torch.float32, device=x.device)
         dd = torch.zeros(H, dtype=torch.float32, device=x.device)
-        if heads != 1:
-            K = int(heads)
-            self.gat_head_width(H, K)
-            ws = self._aggr_workspace("gat_datt", (H, K), lib.glass_gat_datt_mh_ws_bytes(self.n_node, H))
-            rc = lib.glass_gat_datt_mh_f32(x.data_ptr(), ldx, self._gat_mat(da, self.n_node, K, "da"),
-                                           self._gat_mat(db, self.n_node, K, "db"), ds.data_ptr(), dd.data_ptr(), self.n_node, H, K,
-                                           ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, "glass_gat_datt_mh_f32")
-            return ds, dd
-        ws = self._aggr_workspace("gat_datt", H, lib.glass_gat_datt_ws_bytes(self.n_node, H))
-        rc = lib.glass_gat_datt_f32(x.data_ptr(), ldx, self._gat_vec(da, self.n_node, "da"), self._gat_vec(db, self.n_node, "db"),
-                                    ds.data_ptr(), dd.data_ptr(), self.n_node, H, ws.data_ptr(),
-                                    torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_gat_datt_f32")
+        entry = f"glass_gat_datt{mh}_f32"
+        ws = self._aggr_ws.fetch("gat_datt", (H, *kdim), getattr(_lib.load(), f"glass_gat_datt{mh}_ws_bytes")(self.n_node, H))
+        _run(entry, (x.data_ptr(), ldx, tmp(da, self.n_node, "da"), tmp(db, self.n_node, "db"), ds.data_ptr(), dd.data_ptr(),
+                     self.n_node, H, *kdim, ws.data_ptr()))
         return ds, dd
 
     def to_dense(self):
@@ -842,11 +726,8 @@ class Selection:
         Returns (G, partials pointer, device pointer of the plan's reduce list, number of reduce rows)."""
         op = self.op
         H = x.shape[1]
-        G = torch.empty((op.n_rows, H), dtype=torch.float32, device=x.device)
-        ws = op.workspace(H)
-        rc = _lib.load().glass_spmm_csr_f32(op.rowptr.data_ptr(), op.col.data_ptr(), op.val.data_ptr(), x.data_ptr(),
-                                            x.stride(0), G.data_ptr(), G.stride(0), op.n_rows, H,
-                                            self._hdr_noreduce.ctypes.data, op.plan.data_ptr(), ws.data_ptr(),
-                                            torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "glass_spmm_csr_f32")
+        G = _empty(x, op.n_rows, H)
+        # (on op.workspace(H): the size does not depend on the reduce rows)
+        ws = _launch(op, op._ws, "spmm", "glass_spmm_csr_f32", "glass_spmm_ws_bytes",
+                     (x.data_ptr(), x.stride(0), G.data_ptr(), G.stride(0)), H, header=self._hdr_noreduce)
         return G, ws.data_ptr(), op.plan.data_ptr() + 4 * self._off_reduce, self._n_reduce

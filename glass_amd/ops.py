@@ -148,6 +148,30 @@ def maxzoz(n_nodes, pos):
 # ---------------------------------------------------------------------------------------------
 # K1  aggregation
 # ---------------------------------------------------------------------------------------------
+# aggr -> (why ops.spmm and ops.spmm_rep do not serve it, the call that does).  "max" is not here: ops.spmm serves it.
+_OWN_CALL = {
+    "softmax": ("has no temperature of its own", "ops.spmm_softmax(adj, x, t)"),
+    "gat": ("has no attention vectors of its own", "ops.spmm_gat(adj, x, att_src, att_dst, slope)"),
+    "std": ("is no product", "ops.spmm_moments(adj, x, kind, eps)"),
+    "var": ("is no product", "ops.spmm_moments(adj, x, kind, eps)"),
+    "pna": ("is no product", "ops.spmm_pna(adj, x, eps)"),
+}
+
+
+def _need_aggr(adj, what, *aggrs):
+    """ops.`what` serves the adjacencies built for `aggrs`, and no other"""
+    aggr = getattr(adj, "aggr", None)
+    if aggr not in aggrs:
+        raise GlassHipError(f"{what}: the adjacency was built for aggr {aggr!r}, not " + " or ".join(repr(a) for a in aggrs))
+
+
+def _need_weighted(adj, what, thing):
+    """`thing` exists for the aggregations that are products with K2's values only"""
+    aggr = getattr(adj, "aggr", None)
+    if aggr not in _lib.AGGR_MODES:
+        raise GlassHipError(f"{what}: no {thing} for aggr {aggr!r} (only 'sum', 'mean', 'gcn')")
+
+
 class SpMMFn(torch.autograd.Function):
     """y = A @ x with A a graph.CSRAdj; backward dx = A^T @ dy (A carries no gradient:
     edge weights never require grad in the reference, datasets.py:126,226)."""
@@ -208,8 +232,7 @@ class SpMMSoftmaxFn(torch.autograd.Function):
 def spmm_softmax(adj, x, t):
     """Softmax neighbour aggregation: `adj` a graph.CSRAdj built for aggr "softmax", t one fp32 on the device (a parameter, or
     any tensor of one element)."""
-    if getattr(adj, "aggr", None) != "softmax":
-        raise GlassHipError(f"spmm_softmax: the adjacency was built for aggr {getattr(adj, 'aggr', None)!r}, not 'softmax'")
+    _need_aggr(adj, "spmm_softmax", "softmax")
     return SpMMSoftmaxFn.apply(adj, x, t)
 
 
@@ -236,23 +259,25 @@ class SpMMMomentFn(torch.autograd.Function):
         return None, ctx.adj.moment_bwd(x, mu, A, C), None, None
 
 
-def moment_factors(kind, s, wsum, ds, dmu=None):
-    """(A, C) of K1v's backward from the forward's results and the gradients of S and Mu (either may be None) — per destination,
-    N * H work: std: A = dS / (W S); var: A = 2 dS / W; C = dMu / W (None without dMu); a row without entries gives 0."""
+def _live_quotients(s, wsum):
+    """(w, q) for K1v's and K1p's factors: w = W as a column, q(g, den) = where(W > 0, g / den, 0) — a row without entries
+    (W = 0, and den with it) gives 0, not 0 / 0"""
     w = wsum[:, None]
     live = w > 0
     one = torch.ones((), dtype=s.dtype, device=s.device)
-    if ds is None:
-        A = torch.zeros_like(s)
-    else:
-        ds, _ = _rows(ds)
-        den = w * s if kind == "std" else (0.5 * w).expand_as(s)
-        A = torch.where(live, ds / torch.where(live, den, one), torch.zeros_like(ds)).contiguous()
-    C = None
-    if dmu is not None:
-        dmu, _ = _rows(dmu)
-        C = torch.where(live, dmu / torch.where(live, w, one), torch.zeros_like(dmu)).contiguous()
-    return A, C
+
+    def q(g, den):
+        g, _ = _rows(g)
+        return torch.where(live, g / torch.where(live, den, one), torch.zeros_like(g)).contiguous()
+    return w, q
+
+
+def moment_factors(kind, s, wsum, ds, dmu=None):
+    """(A, C) of K1v's backward from the forward's results and the gradients of S and Mu (either may be None) — per destination,
+    N * H work: std: A = dS / (W S); var: A = 2 dS / W; C = dMu / W (None without dMu); a row without entries gives 0."""
+    w, q = _live_quotients(s, wsum)
+    A = torch.zeros_like(s) if ds is None else q(ds, w * s if kind == "std" else (0.5 * w).expand_as(s))
+    return A, (None if dmu is None else q(dmu, w))
 
 
 def spmm_moments(adj, x, kind="std", eps=1e-5):
@@ -260,8 +285,7 @@ def spmm_moments(adj, x, kind="std", eps=1e-5):
     and channel the weighted standard deviation sqrt(Var + eps) (kind "std") or the weighted variance (kind "var"), and the
     weighted mean; zeros for a node without in-edges.  Differentiable in x through both results; under no_grad, or when x needs
     no gradient, nothing of the backward is launched."""
-    if getattr(adj, "aggr", None) not in ("std", "var"):
-        raise GlassHipError(f"spmm_moments: the adjacency was built for aggr {getattr(adj, 'aggr', None)!r}, not 'std' or 'var'")
+    _need_aggr(adj, "spmm_moments", "std", "var")
     if kind not in ("std", "var"):
         raise ValueError(f"spmm_moments: kind must be 'std' or 'var', not {kind!r}")
     return SpMMMomentFn.apply(adj, x, kind, float(eps))
@@ -302,17 +326,9 @@ class SpMMPnaFn(torch.autograd.Function):
 def pna_factors(s, wsum, ds, dmu):
     """(A, C) of K1p's backward from the forward's results and the gradients of S and Mu (either may be None: zeros) — per
     destination, N * H work: A = dS / (W S), C = dMu / W; a row without entries gives 0."""
-    w = wsum[:, None]
-    live = w > 0
-    one = torch.ones((), dtype=s.dtype, device=s.device)
-    out = []
-    for g, den in ((ds, w * s), (dmu, w.expand_as(s))):
-        if g is None:
-            out.append(torch.zeros_like(s))
-        else:
-            g, _ = _rows(g)
-            out.append(torch.where(live, g / torch.where(live, den, one), torch.zeros_like(g)).contiguous())
-    return out[0], out[1]
+    w, q = _live_quotients(s, wsum)
+    A, C = (torch.zeros_like(s) if g is None else q(g, den) for g, den in ((ds, w * s), (dmu, w.expand_as(s))))
+    return A, C
 
 
 def spmm_pna(adj, x, eps=1e-5):
@@ -320,8 +336,7 @@ def spmm_pna(adj, x, eps=1e-5):
     and channel the weighted mean, the largest and the smallest neighbour message, and the weighted standard deviation
     sqrt(Var + eps); zeros for a node without in-edges.  Differentiable in x through all four; under no_grad, when x needs no
     gradient, or when no result received one, nothing of the backward is launched."""
-    if getattr(adj, "aggr", None) != "pna":
-        raise GlassHipError(f"spmm_pna: the adjacency was built for aggr {getattr(adj, 'aggr', None)!r}, not 'pna'")
+    _need_aggr(adj, "spmm_pna", "pna")
     return SpMMPnaFn.apply(adj, x, float(eps))
 
 
@@ -392,8 +407,7 @@ def spmm_gat(adj, x, att_src, att_dst, slope=0.2, heads=1):
     channels (head h: columns [h D, (h + 1) D), D = width / K, of x, the result and both vectors), each with its own softmax;
     K must divide the width and D be a power of two in [4, 256] (ValueError otherwise, before any launch).  heads = 1 is
     single-head attention at any width."""
-    if getattr(adj, "aggr", None) != "gat":
-        raise GlassHipError(f"spmm_gat: the adjacency was built for aggr {getattr(adj, 'aggr', None)!r}, not 'gat'")
+    _need_aggr(adj, "spmm_gat", "gat")
     if heads != 1:
         from .graph import CSRAdj
         if int(heads) != heads:
@@ -434,9 +448,7 @@ def spmm_w(adj, x, w):
     """Aggregation at live edge weights: `adj` a graph.CSRAdj built for aggr "sum", "mean" or "gcn" (its structure is used, its
     stored values are not), w fp32 [E] on the device in the order of the edge_index the adjacency was built from.  The result
     has the bits ops.spmm gives on an adjacency built from w, and is differentiable in x and in w."""
-    aggr = getattr(adj, "aggr", None)
-    if aggr not in _lib.AGGR_MODES:
-        raise GlassHipError(f"spmm_w: no edge-weight gradient for aggr {aggr!r} (only 'sum', 'mean', 'gcn')")
+    _need_weighted(adj, "spmm_w", "edge-weight gradient")
     if (not isinstance(w, torch.Tensor) or w.dim() != 1 or w.shape[0] != adj.nnz or w.dtype != torch.float32 or
             w.device != adj.fwd.rowptr.device):
         got = f"{tuple(w.shape)} {w.dtype} on {w.device}" if isinstance(w, torch.Tensor) else type(w).__name__
@@ -478,9 +490,7 @@ class SpMMDropFn(torch.autograd.Function):
 
 
 def _dropedge_args(adj, p, what):
-    aggr = getattr(adj, "aggr", None)
-    if aggr not in _lib.AGGR_MODES:
-        raise GlassHipError(f"{what}: no edge dropout for aggr {aggr!r} (only 'sum', 'mean', 'gcn')")
+    _need_weighted(adj, what, "edge dropout")
     p = float(p)
     if not (0.0 <= p < 1.0):
         raise ValueError(f"{what}: the edge dropout rate must lie in [0, 1), got {p!r}")
@@ -510,17 +520,12 @@ def edge_keep_mask(adj, p, call_id, symmetric=True):
 
 
 def spmm(adj, x):
-    if getattr(adj, "aggr", None) == "max":
+    aggr = getattr(adj, "aggr", None)
+    if aggr == "max":
         return SpMMMaxFn.apply(adj, x)
-    if getattr(adj, "aggr", None) == "softmax":
-        raise GlassHipError("spmm: a softmax adjacency has no temperature of its own; call ops.spmm_softmax(adj, x, t)")
-    if getattr(adj, "aggr", None) == "gat":
-        raise GlassHipError("spmm: a gat adjacency has no attention vectors of its own; call "
-                            "ops.spmm_gat(adj, x, att_src, att_dst, slope)")
-    if getattr(adj, "aggr", None) in ("std", "var"):
-        raise GlassHipError(f"spmm: a {adj.aggr} adjacency is no product; call ops.spmm_moments(adj, x, kind, eps)")
-    if getattr(adj, "aggr", None) == "pna":
-        raise GlassHipError("spmm: a pna adjacency is no product; call ops.spmm_pna(adj, x, eps)")
+    if aggr in _OWN_CALL:
+        why, call = _OWN_CALL[aggr]
+        raise GlassHipError(f"spmm: a {aggr} adjacency {why}; call {call}")
     return SpMMFn.apply(adj, x)
 
 
@@ -1332,17 +1337,9 @@ class SpMMRepFn(torch.autograd.Function):
 
 
 def spmm_rep(adj, x, R):
-    if getattr(adj, "aggr", None) == "max":
-        raise GlassHipError("replicated max aggregation is not built: aggr 'max' runs one graph at a time (no exact "
-                            "zero-one labels / --use_zeroone with it)")
-    if getattr(adj, "aggr", None) == "softmax":
-        raise GlassHipError("replicated softmax aggregation is not built: aggr 'softmax' runs one graph at a time (no exact "
-                            "zero-one labels / --use_zeroone with it)")
-    if getattr(adj, "aggr", None) == "gat":
-        raise GlassHipError("replicated gat aggregation is not built: aggr 'gat' runs one graph at a time (no exact "
-                            "zero-one labels / --use_zeroone with it)")
-    if getattr(adj, "aggr", None) in ("std", "var", "pna"):
-        raise GlassHipError(f"replicated {adj.aggr} aggregation is not built: aggr '{adj.aggr}' runs one graph at a time (no exact "
+    aggr = getattr(adj, "aggr", None)
+    if aggr == "max" or aggr in _OWN_CALL:
+        raise GlassHipError(f"replicated {aggr} aggregation is not built: aggr '{aggr}' runs one graph at a time (no exact "
                             "zero-one labels / --use_zeroone with it)")
     return SpMMRepFn.apply(adj, x, int(R))
 

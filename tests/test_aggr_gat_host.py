@@ -219,7 +219,7 @@ def test_names_are_accepted_where_the_aggregation_is_chosen():
         ops.spmm_gat(_Adj(), torch.zeros(2, 4), torch.zeros(4), torch.zeros(4), 0.2)
     for what in ("gat_scores", "gat_fwd", "gat_edge", "gat_bwd", "gat_da", "gat_datt"):
         with pytest.raises(_lib.GlassHipError, match="not 'gat'"):
-            graph.CSRAdj._need_gat(_Adj(), what)
+            graph.CSRAdj._need(_Adj(), what, "gat")
 
 
 def test_the_attention_vectors_are_parameters_of_gat_layers_only():

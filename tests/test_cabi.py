@@ -28,6 +28,51 @@ def test_library_exports_every_declared_symbol():
     assert lib.glass_version() == _lib.ABI_VERSION == 6
 
 
+def declared_prototypes():
+    """name -> (return kind, [parameter kinds]) of every `ret name(args);` in include/glass_hip.h.  Kinds: "ptr", "i64", "i32"
+    (int and int32_t), "u64", "f32", "f64"; a type this does not know raises KeyError."""
+    text = open(os.path.join(ROOT, "include", "glass_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"^[ \t]*#[^\n]*", "", text, flags=re.M)
+    scalar = {"int64_t": "i64", "int": "i32", "int32_t": "i32", "uint64_t": "u64", "float": "f32", "double": "f64"}
+
+    def kind(decl, named):
+        if "*" in decl:
+            return "ptr"
+        words = [w for w in decl.split() if w != "const"]
+        assert len(words) == (2 if named else 1), decl
+        return scalar[words[0]]
+    protos = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(glass_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        params = [p.strip() for p in args.split(",")]
+        params = [] if params in ([""], ["void"]) else params
+        assert name not in protos, name
+        protos[name] = (kind(ret, False), [kind(p, True) for p in params])
+    return protos
+
+
+def _ctypes_kind(t):
+    from ctypes import c_void_p, c_char_p, c_int64, c_int, c_uint64, c_float, c_double
+    if t in (c_void_p, c_char_p) or issubclass(t, ctypes._Pointer):
+        return "ptr"
+    return {c_int64: "i64", c_int: "i32", c_uint64: "u64", c_float: "f32", c_double: "f64"}[t]
+
+
+def test_ctypes_table_mirrors_every_prototype_argument_by_argument():
+    """A cdecl call through ctypes takes extra arguments without a word and converts each one by the table, so the table is
+    held to the header in return kind, argument count and the kind at every position — not in names alone."""
+    from glass_amd import _lib
+    protos = declared_prototypes()
+    assert len(protos) >= len(_lib.SIGNATURES) >= 16, "the pattern finds fewer prototypes than the table has names"
+    for name, (res, args) in _lib.SIGNATURES.items():
+        ret, params = protos[name]
+        assert _ctypes_kind(res) == ret, f"{name}: returns {ret} in the header"
+        assert len(args) == len(params), f"{name}: {len(params)} parameters in the header, {len(args)} in the table"
+        for i, (a, p) in enumerate(zip(args, params)):
+            assert _ctypes_kind(a) == p, f"{name}: parameter {i} is {p} in the header"
+
+
 def test_header_cites_reference_lines():
     text = open(os.path.join(ROOT, "include", "glass_hip.h")).read()
     for cite in ("impl/models.py:164", "impl/models.py:83-111", "impl/utils.py:32-45", "impl/models.py:346-350"):
