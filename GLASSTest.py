@@ -52,17 +52,18 @@ def parse_args(argv=None):
                         "split's label counts, applied inside the fused loss (default: none)")
     p.add_argument("--pool", type=str, default=None, choices=tuple(POOLS),
                    help="(extension) readout instead of the config file's `pool` (default: the config's value)")
-    p.add_argument("--aggr", type=str, default=None, choices=("mean", "sum", "gcn", "max", "softmax", "gat", "std", "var", "pna"),
+    p.add_argument("--aggr", type=str, default=None, choices=("mean", "sum", "gcn", "max", "softmax", "gat", "gatv2", "std", "var", "pna"),
                    help="(extension) neighbour aggregation instead of the config file's `aggr` (default: the config's value); "
                         "max: the largest weighted neighbour message per channel; softmax: the softmax-weighted mean of the "
                         "messages with a learned temperature per layer (positive edge weights); gat: attention (--gat_heads heads), "
-                        "the weights from two learned vectors per layer (positive edge weights); std / var: the weighted standard "
+                        "the weights from two learned vectors per layer (positive edge weights); gatv2: dynamic attention, one head, the "
+                        "score of an edge from one learned vector per layer applied after the non-linearity (positive edge weights); std / var: the weighted standard "
                         "deviation / variance of the messages (positive edge weights); pna: mean, max, min and standard deviation of the "
                         "messages under three degree scalers, mixed per channel by a learned [12, hidden] weight per layer "
-                        "(positive edge weights); none of the six is available "
+                        "(positive edge weights); none of the seven is available "
                         "with --use_zeroone")
     p.add_argument("--gat_slope", type=float, default=0.2,
-                   help="(extension) LeakyReLU's negative slope in the attention scores of --aggr gat (default: 0.2)")
+                   help="(extension) LeakyReLU's negative slope in the attention scores of --aggr gat and gatv2 (default: 0.2)")
     p.add_argument("--gat_heads", type=int, default=1,
                    help="(extension) attention heads of --aggr gat: they partition the hidden channels, so the count must divide "
                         "hidden_dim and leave a power of two in [4, 256] channels per head (default: 1)")

@@ -118,6 +118,18 @@ SIGNATURES = {
     "glass_spmm_gat_mh_da_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, c_int, _P, _P, _P, _P]),
     "glass_gat_datt_mh_ws_bytes": (c_int64, [_I, _I]),
     "glass_gat_datt_mh_f32": (c_int, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    # (K1a2, aggr "gatv2": one attention vector, the score of an entry kept in s [nnz])
+    "glass_spmm_gatv2_score_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_gatv2_score_f32": (c_int, [_P, _P, _P, _P, _I, _P, c_float, _P, _I, _I, _P, _P, _P, _P]),
+    "glass_spmm_gatv2_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_gatv2_csr_f32": (c_int, [_P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "glass_spmm_gatv2_edge_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_gatv2_edge_f32": (c_int, [_P, _P, _P, _P, _I, _P, c_float, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P,
+                                          _P]),
+    "glass_spmm_gatv2_bwd_ws_bytes": (c_int64, [_P, _I]),
+    "glass_spmm_gatv2_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _I, _P, c_float, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "glass_spmm_gatv2_datt_ws_bytes": (c_int64, [_I, _I]),
+    "glass_spmm_gatv2_datt_f32": (c_int, [_P, _P, _I, _I, _P, _P]),
     "glass_adj_values_f32": (c_int, [_P, _P, _P, _I, c_int, _P, _P, _P]),
     "glass_spmm_dval_ws_bytes": (c_int64, [_P, _I]),
     "glass_spmm_dval_f32": (c_int, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P]),

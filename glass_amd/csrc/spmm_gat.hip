@@ -105,26 +105,6 @@ struct GatFwdOp {
     }
 };
 
-// rows cut into several chunks: their partials merged slot by slot
-__global__ __launch_bounds__(kBlock) void spmm_gat_reduce_kernel(const float* __restrict__ ps, const float* __restrict__ pm,
-                                                                 const float* __restrict__ pz, float* __restrict__ Y,
-                                                                 int64_t ldy, float* __restrict__ L, int H,
-                                                                 const int32_t* __restrict__ rrows) {
-    const int32_t* rr = rrows + 3 * (int64_t)blockIdx.x;
-    const int row = rr[0], first = rr[1], n = rr[2];
-    for (int c = threadIdx.x; c < H; c += kBlock) {
-        GatAcc<1> p;
-        p.init();
-        for (int k = 0; k < n; ++k) {
-            const float os[1] = {ps[(int64_t)(first + k) * H + c]};
-            p.merge(pm[first + k], pz[first + k], os);
-        }
-        const bool any = p.z > 0.f;
-        Y[(int64_t)row * ldy + c] = any ? p.s[0] / p.z : 0.f;
-        if (c == 0) L[row] = any ? p.m + logf(p.z) : 0.f;
-    }
-}
-
 // ---- edge pass: g_e for every entry of the forward CSR, db_i for every row ---------------------------------------------------
 // One column tile (gridDim.y = 1): lane `sub` of a group owns columns (p * LPR + sub) * VW ... of every column pass p.  The row's
 // dY of pass 0 stays in registers; further passes (H beyond LPR * VW columns: LPR = 64 then, one group per wave) re-read it.
@@ -394,7 +374,7 @@ template <int VW, int LPR>
 static int launch_gat_fwd(GatFwdOp<VW, LPR> op, const int32_t* rowptr, const int32_t* hdr, const int32_t* plan, hipStream_t st) {
     launch_items(op, rowptr, hdr, plan, st);
     if (hdr[H_NREDUCE] > 0)
-        hipLaunchKernelGGL(spmm_gat_reduce_kernel, dim3((unsigned)hdr[H_NREDUCE]), dim3(kBlock), 0, st, op.ps, op.pm, op.pz, op.Y,
+        hipLaunchKernelGGL(spmm_gat_reduce_kernel<>, dim3((unsigned)hdr[H_NREDUCE]), dim3(kBlock), 0, st, op.ps, op.pm, op.pz, op.Y,
                            op.ldy, op.L, op.H, plan + hdr[H_OFF_REDUCE]);
     return launch_status("glass_spmm_gat_csr_f32");
 }

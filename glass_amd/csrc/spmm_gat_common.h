@@ -82,6 +82,28 @@ struct GatAcc {
     }
 };
 
+// rows cut into several chunks, forward: their partials merged slot by slot (a template only for its linkage: this header is
+// included by several translation units)
+template <int = 0>
+__global__ __launch_bounds__(kBlock) void spmm_gat_reduce_kernel(const float* __restrict__ ps, const float* __restrict__ pm,
+                                                                 const float* __restrict__ pz, float* __restrict__ Y,
+                                                                 int64_t ldy, float* __restrict__ L, int H,
+                                                                 const int32_t* __restrict__ rrows) {
+    const int32_t* rr = rrows + 3 * (int64_t)blockIdx.x;
+    const int row = rr[0], first = rr[1], n = rr[2];
+    for (int c = threadIdx.x; c < H; c += kBlock) {
+        GatAcc<1> p;
+        p.init();
+        for (int k = 0; k < n; ++k) {
+            const float os[1] = {ps[(int64_t)(first + k) * H + c]};
+            p.merge(pm[first + k], pz[first + k], os);
+        }
+        const bool any = p.z > 0.f;
+        Y[(int64_t)row * ldy + c] = any ? p.s[0] / p.z : 0.f;
+        if (c == 0) L[row] = any ? p.m + logf(p.z) : 0.f;
+    }
+}
+
 // ---- the transposed pass's state: da's partial sum beside VW running sums ---------------------------------------------------
 template <int VW>
 struct GatBwdAcc {

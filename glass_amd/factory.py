@@ -9,7 +9,7 @@ def build_glass(hidden, layers, max_deg, out_ch, aggr, pool, z_ratio, dropout=0.
                 live_edge_weight=False, moment_eps=1e-5, edge_dropout=0.0):
     """pad_width: a hidden width no kernel family serves (33..63, 65..127, ...) is built at the next family width with
     zero padding — exact, same logical parameters, logical state_dict (glass_amd/widths.py); False keeps the width as it
-    is (the per-op path with library GEMMs serves it).  gat_heads: the attention heads of aggr "gat" (GLASSConv).
+    is (the per-op path with library GEMMs serves it).  gat_heads: the attention heads of aggr "gat" (GLASSConv; aggr "gatv2" has one).
     live_edge_weight: the layers aggregate with each call's edge weights, differentiably (GLASSConv).  moment_eps: the
     constant under the root of aggr "std" (GLASSConv).  edge_dropout: the share of adjacency entries every layer drops in each
     training forward (DropEdge; GLASSConv: aggr "sum" / "mean" / "gcn", not with live_edge_weight)."""

@@ -9,12 +9,12 @@ HBM layout (all on the device the graph lives on):
   rowptr int32[N+1], col int32[nnz], val fp32[nnz]            CSR of A   (row = destination)
   rowptr_t, col_t, val_t                                      CSR of A^T (for the backward)
   plan / plan_t int32[...]                                    opaque K1 schedules
-  eid_t int32[nnz]                                            aggr "max", "gat" and "pna": forward index of each entry of A^T
+  eid_t int32[nnz]                                            aggr "max", "gat", "gatv2" and "pna": forward index of each entry of A^T
   perm int64[nnz]                                             the build permutation: entry e is the caller's edge perm[e]
 aggr "sum", "mean" and "gcn" can also be evaluated at OTHER edge weights on the same structure, with the gradient with respect
 to them (values_of / dval / colsum / values_bwd: K1w, ops.spmm_w); what that needs beyond perm is built on first use.
-aggr "max", "softmax", "gat", "std", "var" and "pna" keep the raw edge weights in val (the values of "sum"); all but "max"
-require them > 0.
+aggr "max", "softmax", "gat", "gatv2", "std", "var" and "pna" keep the raw edge weights in val (the values of "sum"); all but
+"max" require them > 0.
 Duplicate (row,col) entries are kept as separate entries: they add up in the product exactly as in
 the reference's uncoalesced COO matmul.
 
@@ -210,7 +210,7 @@ def _pna_degrees(rowptr, w):
     return delta, torch.from_numpy(W.astype(np.float32)).to(rowptr.device)
 
 
-_RAW_AGGR = ("max", "softmax", "gat", "std", "var", "pna")  # the extensions: raw edge weights in val, kernels of their own
+_RAW_AGGR = ("max", "softmax", "gat", "gatv2", "std", "var", "pna")  # the extensions: raw edge weights in val, kernels of their own
 MOMENT_KINDS = {"std": 0, "var": 1}
 
 
@@ -222,7 +222,8 @@ class CSRAdj:
     extension): the raw weights too, strictly positive (checked here, once), aggregated by K1s (softmax_fwd / softmax_bwd /
     softmax_dt) with a temperature the caller owns.  aggr "gat" (an extension): built like "softmax", aggregated by K1a
     (gat_scores / gat_fwd / gat_edge / gat_bwd / gat_datt, each with heads=K for multi-head attention) with two attention
-    vectors the caller owns.  aggr "std" / "var" (extensions): built like "softmax", aggregated by K1v (moment_fwd /
+    vectors the caller owns.  aggr "gatv2" (an extension): built like "gat", aggregated by K1a2 (gatv2_score / gatv2_fwd /
+    gatv2_edge / gatv2_bwd / gatv2_datt) with one attention vector the caller owns.  aggr "std" / "var" (extensions): built like "softmax", aggregated by K1v (moment_fwd /
     moment_bwd: the weighted standard deviation or variance of the neighbour messages, with their weighted mean).  aggr "pna"
     (an extension): built like "softmax", aggregated by K1p (pna_fwd / pna_bwd: mean, standard deviation, max and min of the
     neighbour messages from one gather); `pna_delta` is the mean of log(W_i + 1) over the rows with entries (PNA's degree
@@ -245,7 +246,7 @@ class CSRAdj:
         perm = torch.argsort(row * n + col, stable=True)
         row, col = row[perm], col[perm]
         w = edge_weight.to(torch.float32)[perm].contiguous()
-        if aggr in ("softmax", "gat") and not bool((w > 0).all()):  # one device read; the kernels do not test it
+        if aggr in ("softmax", "gat", "gatv2") and not bool((w > 0).all()):  # one device read; the kernels do not test it
             raise ValueError(f"aggr {aggr!r}: edge weights are multiplicities and must be strictly positive")
         rowptr = _csr_from_sorted(row, n)
         col32 = col.to(torch.int32).contiguous()
@@ -264,7 +265,7 @@ class CSRAdj:
         self.bwd = CSROperand(rowptr_t, col_t, val_t, n, n)
         if aggr in _lib.AGGR_MODES:
             self._raw_w = val if aggr == "sum" else w  # the raw weights, forward entry order (edge dropout redraws from them)
-        if aggr in ("max", "gat", "pna"):
+        if aggr in ("max", "gat", "gatv2", "pna"):
             self.eid_t = perm_t.to(torch.int32).contiguous()  # transposed entry t is forward entry eid_t[t]
         if aggr in _RAW_AGGR:
             self._aggr_ws = _Workspaces(dev)
@@ -690,6 +691,79 @@ class CSRAdj:
         _run(entry, (x.data_ptr(), ldx, tmp(da, self.n_node, "da"), tmp(db, self.n_node, "db"), ds.data_ptr(), dd.data_ptr(),
                      self.n_node, H, *kdim, ws.data_ptr()))
         return ds, dd
+
+    # ---- K1a2: aggr "gatv2" (csrc/spmm_gatv2.hip) ---------------------------------------------------------------------------
+    # (an adjacency without entries launches nothing: the entries return at once, and the results, all zero, are made here)
+    def _gatv2_out(self, like, *shape):
+        return (torch.zeros if self.nnz == 0 else torch.empty)(shape, dtype=torch.float32, device=like.device)
+
+    def gatv2_score(self, x, att, slope):
+        """s [nnz] = K1a2 score pass: per entry of the forward CSR the dot of att with LeakyReLU(x[destination] + x[source]),
+        in forward entry order (products and sum in fp64, rounded once).  Every later pass reads it."""
+        self._need("gatv2_score", "gatv2")
+        op = self.fwd
+        ldx = _operand(x, op.n_cols, "X")
+        H = x.shape[1]
+        s = _empty(x, max(op.nnz, 1))[:op.nnz]
+        _launch(op, self._aggr_ws, "gatv2_score", "glass_spmm_gatv2_score_f32", "glass_spmm_gatv2_score_ws_bytes",
+                (x.data_ptr(), ldx, self._gat_vec(att, H, "att"), float(slope), s.data_ptr()), H)
+        return s
+
+    def gatv2_fwd(self, x, s):
+        """(y, lse) = K1a2 forward: per destination the attention-weighted mean of the neighbour messages, the weights a softmax
+        over the row's entries of s; lse [N] = max + log of the weighted sum of exponentials, kept for the backward."""
+        self._need("gatv2_fwd", "gatv2")
+        op = self.fwd
+        ldx = _operand(x, op.n_cols, "X")
+        H = x.shape[1]
+        y = self._gatv2_out(x, op.n_rows, H)
+        lse = self._gatv2_out(x, op.n_rows)
+        _launch(op, self._aggr_ws, "gatv2_fwd", "glass_spmm_gatv2_csr_f32", "glass_spmm_gatv2_ws_bytes",
+                (x.data_ptr(), ldx, self._gat_vec(s, op.nnz, "s"), y.data_ptr(), H, lse.data_ptr()), H)
+        return y, lse
+
+    def gatv2_edge(self, dy, x, y, lse, s, att, slope):
+        """(g, p, gd, r) = K1a2 edge pass over the forward CSR, one gather of x[source] per entry: p [nnz] the attention weights,
+        g [nnz] the score gradients, gd [N, H] the destination side of dx (the row sums of g att f) and r [N, H] the row sums
+        of g LeakyReLU(x[destination] + x[source]), whose column sums are att's gradient."""
+        self._need("gatv2_edge", "gatv2")
+        op = self.fwd
+        ldx = _operand(x, op.n_cols, "X")
+        lddy, ldy = (_operand(t, op.n_rows, n) for t, n in ((dy, "dY"), (y, "Y")))
+        assert dy.shape == x.shape == y.shape
+        H = x.shape[1]
+        g = _empty(x, max(op.nnz, 1))[:op.nnz]
+        p = _empty(x, max(op.nnz, 1))[:op.nnz]
+        gd = self._gatv2_out(x, op.n_rows, H)
+        r = self._gatv2_out(x, op.n_rows, H)
+        _launch(op, self._aggr_ws, "gatv2_edge", "glass_spmm_gatv2_edge_f32", "glass_spmm_gatv2_edge_ws_bytes",
+                (x.data_ptr(), ldx, self._gat_vec(att, H, "att"), float(slope), self._gat_vec(s, op.nnz, "s"), dy.data_ptr(), lddy,
+                 y.data_ptr(), ldy, self._gat_vec(lse, op.n_rows, "L"), g.data_ptr(), p.data_ptr(), gd.data_ptr(), r.data_ptr()), H)
+        return g, p, gd, r
+
+    def gatv2_bwd(self, dy, x, p, g, gd, att, slope):
+        """dx = K1a2 transposed pass: dx[j] = the sum over the entries that read x[j] of p dy[destination] + g att f, plus gd[j]."""
+        self._need("gatv2_bwd", "gatv2")
+        op = self.bwd
+        lddy = _operand(dy, op.n_cols, "dY")
+        ldx = _operand(x, op.n_rows, "X")
+        H = dy.shape[1]
+        assert gd.shape == (op.n_rows, H) and gd.is_contiguous() and gd.dtype == torch.float32 and gd.is_cuda, "gd"
+        dx = self._gatv2_out(dy, op.n_rows, H)
+        _launch(op, self._aggr_ws, "gatv2_bwd", "glass_spmm_gatv2_bwd_f32", "glass_spmm_gatv2_bwd_ws_bytes",
+                (x.data_ptr(), ldx, self._gat_vec(att, H, "att"), float(slope), dy.data_ptr(), lddy, self._gat_vec(p, op.nnz, "p"),
+                 self._gat_vec(g, op.nnz, "g"), gd.data_ptr(), dx.data_ptr(), H), H, eid_t=self.eid_t)
+        return dx
+
+    def gatv2_datt(self, r):
+        """datt [H] = the column sums of r (fp64 partials, a fixed order): att's gradient, run only when it is trained."""
+        self._need("gatv2_datt", "gatv2")
+        n, H = self.n_node, r.shape[1]
+        assert r.shape == (n, H) and r.is_contiguous() and r.dtype == torch.float32 and r.is_cuda, "r"
+        datt = torch.zeros(H, dtype=torch.float32, device=r.device)
+        ws = self._aggr_ws.fetch("gatv2_datt", (H, ), _lib.load().glass_spmm_gatv2_datt_ws_bytes(n, H))
+        _run("glass_spmm_gatv2_datt_f32", (r.data_ptr(), datt.data_ptr(), n, H, ws.data_ptr()))
+        return datt
 
     def to_dense(self):
         """Dense [N,N] (tests on tiny graphs only)."""

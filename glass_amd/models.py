@@ -9,8 +9,8 @@ Reference map (file:line under /root/reference):
   PoolModule/AddPool/MaxPool/MeanPool/SizePool 275-319 · GLASS 322-355   (impl/models.py)
 Not in the reference: AttnPool (attention readout, pool "attn"); aggr "max" (max neighbour aggregation, buildAdj); aggr
 "softmax" (softmax neighbour aggregation with a learned temperature: the conv layers' parameter `t`); aggr "gat" (attention
-aggregation with `gat_heads` heads: GLASSConv's parameters `att_src` and `att_dst`); aggr "std" / "var" (the weighted standard
-deviation / variance of the neighbour messages, GLASSConv only: no parameter, the constant `moment_eps`); aggr "pna" (PNA:
+aggregation with `gat_heads` heads: GLASSConv's parameters `att_src` and `att_dst`); aggr "gatv2" (dynamic attention, one head:
+GLASSConv's parameter `att`); aggr "std" / "var" (the weighted standard deviation / variance of the neighbour messages, GLASSConv only: no parameter, the constant `moment_eps`); aggr "pna" (PNA:
 mean, max, min and standard deviation of the neighbour messages under three degree scalers, GLASSConv only: its parameter
 `pna_weight` [12, out_channels], the constant `moment_eps`).
 """
@@ -154,7 +154,8 @@ def buildAdj(edge_index, edge_weight, n_node: int, aggr: str):
     (ValueError otherwise), aggregated by ops.spmm_softmax with the layer's temperature.  aggr "std" / "var" (extensions): built
     like "softmax", aggregated by ops.spmm_moments.  aggr "pna" (an extension): built like "softmax", aggregated by
     ops.spmm_pna / ops.pna_mix."""
-    if aggr not in ("mean", "sum", "gcn", "max", "softmax", "gat", "std", "var", "pna"):  # ("gat", an extension: built like "softmax", ops.spmm_gat)
+    # ("gat" / "gatv2", extensions: built like "softmax", ops.spmm_gat / ops.spmm_gatv2)
+    if aggr not in ("mean", "sum", "gcn", "max", "softmax", "gat", "gatv2", "std", "var", "pna"):
         raise NotImplementedError
     for ei, ew, n, a, adj in _adj_cache:
         if ei is edge_index and ew is edge_weight and n == int(n_node) and a == aggr:
@@ -181,6 +182,13 @@ def _reset_gat_att(conv):
         with torch.no_grad():
             conv.att_src.uniform_(-bound, bound)
             conv.att_dst.uniform_(-bound, bound)
+
+
+def _reset_gatv2_att(conv):
+    """The attention vector of a conv layer with aggr "gatv2": xavier_uniform_ on its [1, H] view (in place)."""
+    if conv.aggr == "gatv2":
+        with torch.no_grad():
+            nn.init.xavier_uniform_(conv.att.view(1, -1))
 
 
 def _reset_pna_weight(conv):
@@ -236,6 +244,11 @@ class GLASSConv(nn.Module):
     gat_heads: K heads partition the channels (head h: channels [h D, (h + 1) D), D = out_channels / K, of the messages, the
     result and both vectors), each with its own softmax; the output width and the state_dict do not depend on K.  K must
     divide out_channels and D be a power of two in [4, 256] (ValueError at construction; other aggregations ignore it).
+    aggr "gatv2" (an extension, GATv2): dynamic attention over the mixed messages, one head — the score of an entry is att .
+    LeakyReLU(m[destination] + m[source]), the non-linearity before the dot, so a destination ranks its neighbours in an order
+    of its own.  The layer owns att ([out_channels]) and the constant gat_slope; the state_dict is that of aggr "mean" plus
+    `att`; gat_heads other than 1 is a ValueError at construction; one graph at a time (ValueError with `batch`,
+    live_edge_weight or edge_dropout).
     live_edge_weight (an extension, aggr "sum" / "mean" / "gcn" only: ValueError otherwise): the layer aggregates with the
     `edge_weight` of EACH call (ops.spmm_w: the normalisation is evaluated again, and the result is differentiable in the
     weights) on the structure cached from the first call; no parameter, the same state_dict.  Such a layer runs as per-op
@@ -295,6 +308,11 @@ class GLASSConv(nn.Module):
             self.att_src = nn.Parameter(torch.empty(out_channels))
             self.att_dst = nn.Parameter(torch.empty(out_channels))
             _reset_gat_att(self)
+        if aggr == "gatv2":  # (likewise: only this configuration owns the key)
+            if isinstance(gat_heads, bool) or gat_heads != 1:
+                raise ValueError(f"GLASSConv: aggr 'gatv2' has one attention head, not gat_heads={gat_heads!r}")
+            self.att = nn.Parameter(torch.empty(out_channels))
+            _reset_gatv2_att(self)
 
     def reset_parameters(self):
         for lin in list(self.trans_fns) + list(self.comb_fns):
@@ -302,6 +320,7 @@ class GLASSConv(nn.Module):
         self.gn.reset_parameters()
         _reset_softmax_t(self)
         _reset_gat_att(self)
+        _reset_gatv2_att(self)
         _reset_pna_weight(self)
 
     def forward(self, x_, edge_index, edge_weight, mask, out=None, batch=None):
@@ -311,7 +330,7 @@ class GLASSConv(nn.Module):
         calls key only on the row's label byte and take the R * N rows as they are."""
         if self.live_edge_weight and batch is not None:
             raise ValueError("GLASSConv: live_edge_weight has no replicated form (exact zero-one labels: `batch` given)")
-        if self.aggr in ("std", "var", "pna") and batch is not None:
+        if self.aggr in ("std", "var", "pna", "gatv2") and batch is not None:
             raise ValueError(f"GLASSConv: aggr {self.aggr!r} has no replicated form (exact zero-one labels: `batch` given)")
         p_edge = _check_edge_dropout(self.edge_dropout, self.aggr, self.live_edge_weight)  # (the attributes may have been set since)
         if p_edge > 0 and batch is not None:
@@ -332,6 +351,8 @@ class GLASSConv(nn.Module):
             agg = lambda m: ops.spmm_softmax(self.adj, m, self.t)
         elif self.aggr == "gat":
             agg = lambda m: ops.spmm_gat(self.adj, m, self.att_src, self.att_dst, self.gat_slope, self.gat_heads)
+        elif self.aggr == "gatv2":
+            agg = lambda m: ops.spmm_gatv2(self.adj, m, self.att, self.gat_slope)
         elif self.aggr in ("std", "var"):
             agg = lambda m: ops.spmm_moments(self.adj, m, self.aggr, self.moment_eps)[0]
         elif self.aggr == "pna":

@@ -152,6 +152,7 @@ def maxzoz(n_nodes, pos):
 _OWN_CALL = {
     "softmax": ("has no temperature of its own", "ops.spmm_softmax(adj, x, t)"),
     "gat": ("has no attention vectors of its own", "ops.spmm_gat(adj, x, att_src, att_dst, slope)"),
+    "gatv2": ("has no attention vector of its own", "ops.spmm_gatv2(adj, x, att, slope)"),
     "std": ("is no product", "ops.spmm_moments(adj, x, kind, eps)"),
     "var": ("is no product", "ops.spmm_moments(adj, x, kind, eps)"),
     "pna": ("is no product", "ops.spmm_pna(adj, x, eps)"),
@@ -414,6 +415,43 @@ def spmm_gat(adj, x, att_src, att_dst, slope=0.2, heads=1):
             raise ValueError(f"spmm_gat: heads must be an integer >= 1, not {heads!r}")
         CSRAdj.gat_head_width(x.shape[-1], int(heads))
     return SpMMGatFn.apply(adj, x, att_src, att_dst, slope, int(heads))
+
+
+class SpMMGatV2Fn(torch.autograd.Function):
+    """y[i] = attention-weighted mean of the messages x[col] over the entries of row i of A (aggr "gatv2", K1a2:
+    csrc/spmm_gatv2.hip): the weights are the softmax, times the edge weights, of att . LeakyReLU(x[i] + x[col]) — dynamic
+    attention, the non-linearity before the dot.  The node keeps x, y, the log-sum-exp and the entries' scores; the backward
+    always runs the edge pass, then the transposed pass only when x needs a gradient and the column reduction only when att
+    does (A carries none)."""
+    @staticmethod
+    def forward(ctx, adj, x, att, slope):
+        _need_gpu(x)
+        x, _ = _rows(x)
+        s = adj.gatv2_score(x, att, slope)
+        y, lse = adj.gatv2_fwd(x, s)
+        ctx.adj, ctx.slope = adj, float(slope)
+        ctx.save_for_backward(x, y, lse, s, att)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy, _ = _rows(dy)
+        x, y, lse, s, att = ctx.saved_tensors
+        adj = ctx.adj
+        need_x, need_att = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (need_x or need_att):
+            return None, None, None, None
+        g, p, gd, r = adj.gatv2_edge(dy, x, y, lse, s, att, ctx.slope)
+        dx = adj.gatv2_bwd(dy, x, p, g, gd, att, ctx.slope) if need_x else None
+        datt = adj.gatv2_datt(r) if need_att else None
+        return None, dx, datt, None
+
+
+def spmm_gatv2(adj, x, att, slope=0.2):
+    """Dynamic attention neighbour aggregation (GATv2, one head): `adj` a graph.CSRAdj built for aggr "gatv2", att one fp32
+    vector of x's width on the device (a parameter, or any tensor), slope LeakyReLU's negative slope."""
+    _need_aggr(adj, "spmm_gatv2", "gatv2")
+    return SpMMGatV2Fn.apply(adj, x, att, slope)
 
 
 class SpMMWFn(torch.autograd.Function):

@@ -615,9 +615,10 @@ class StackProgram:
     @staticmethod
     def supported(emb):
         from .models import GLASSConv, EmbGConv, _act_code
-        if any(getattr(c, "aggr", None) in ("max", "softmax", "gat", "std", "var", "pna") for c in emb.convs):
+        if any(getattr(c, "aggr", None) in ("max", "softmax", "gat", "gatv2", "std", "var", "pna") for c in emb.convs):
             # max, softmax, attention, std / var and PNA aggregation are no products: no fused form, the per-op path (ops.spmm
-            # -> K1m, ops.spmm_softmax -> K1s, ops.spmm_gat -> K1a, ops.spmm_moments -> K1v, ops.spmm_pna -> K1p) serves them
+            # -> K1m, ops.spmm_softmax -> K1s, ops.spmm_gat -> K1a, ops.spmm_gatv2 -> K1a2, ops.spmm_moments -> K1v, ops.spmm_pna
+            # -> K1p) serves them
             return False
         if any(getattr(c, "live_edge_weight", False) for c in emb.convs):
             return False  # live edge weights (ops.spmm_w): the program bakes the adjacency's stored values in

@@ -386,6 +386,65 @@ int glass_gat_datt_mh_f32(const float* X, int64_t ldx, const float* da, const fl
                           float* datt_src, float* datt_dst,                              /* [H] each */
                           int64_t n_rows, int64_t H, int64_t K, void* ws, void* stream);
 
+/* K1a2 dynamic attention neighbour aggregation (aggr "gatv2": an extension, the reference has none; single-head GATv2,
+ *     csrc/spmm_gatv2.hip) at the call site K1 serves, on K1's CSR and plans.  Forward CSR as for K1a (raw weights > 0,
+ *     multiplicities; the caller's check).  att: one [H] fp32 vector in device memory; slope: LeakyReLU's negative slope, by
+ *     value.  With u_ec = X[i,c] + X[col[e],c] (one rounded fp32 add), r_ec = u_ec > 0 ? u_ec : slope * u_ec (one rounded
+ *     multiply) and f_ec = u_ec > 0 ? 1 : slope (u == 0 takes slope), for the entries e of row i:
+ *
+ *   glass_spmm_gatv2_score_f32: s[e] = sum_c att[c] r_ec for every entry ([nnz], forward entry order): products and sum in
+ *     fp64 in a fixed order, rounded once.  Every later pass reads s (or p, g): one entry, one score.  No workspace
+ *     (glass_spmm_gatv2_score_ws_bytes is 0 for every plan; ws may be null).
+ *   glass_spmm_gatv2_csr_f32: M = max_e s[e], Z = sum_e val[e] exp(s[e] - M):  Y[i,:] = (sum_e val[e] exp(s[e] - M)
+ *     X[col[e],:]) / Z, L[i] = M + log Z ([n_rows]).  A row without entries: Y = 0, L = 0.  ws: glass_spmm_gatv2_ws_bytes(hdr,
+ *     H) = the plan's partial slots times (H + 2) floats; cut rows are merged by a second launch in slot order.
+ *   glass_spmm_gatv2_edge_f32: on the FORWARD CSR, one gather of X[col[e],:] per entry, with D_i = dY[i,:] . Y[i,:] and q_e =
+ *     dY[i,:] . X[col[e],:]:  p[e] = val[e] exp(s[e] - L[i]) and g[e] = p[e] (q_e - D_i) for every entry ([nnz] each), and the
+ *     row sums Gd[i,c] = sum_e g[e] att[c] f_ec, R[i,c] = sum_e g[e] r_ec ([n_rows, H] each, contiguous; 0 for a row
+ *     without entries).  ws: glass_spmm_gatv2_edge_ws_bytes(hdr, H) = partial slots times 2 H floats.
+ *   glass_spmm_gatv2_bwd_f32: on the TRANSPOSED CSR (row j = source, col_t = destinations i, val_t, eid_t[t] = the forward
+ *     index of transposed entry t, its own plan), per entry the rows dY[i,:] and X[i,:]:  dX[j,c] = sum over the entries of
+ *     ( p[eid_t[t]] dY[i,c] + g[eid_t[t]] att[c] f_ec )  +  Gd[j,c]; a row without entries gets Gd[j,:] (a self-loop takes both
+ *     terms).  ws: glass_spmm_gatv2_bwd_ws_bytes(hdr_t, H) = partial slots times H floats.
+ *   glass_spmm_gatv2_datt_f32: datt[c] = sum_i R[i,c]: fp64 partials per workgroup, a one-workgroup final stage in workgroup
+ *     order, written as fp32.  ws (8-byte aligned): glass_spmm_gatv2_datt_ws_bytes(n_rows, H).
+ *   All: no float atomics, bitwise repeatable for a given plan; att, s, p, g, L, Gd, R are read when the kernels run (a
+ *     captured launch follows the live parameter).  Every H and leading dimension K1a takes (16-byte vector form when H, the
+ *     ld* and the row pointers allow it, scalar form otherwise).  Refused on the host before any launch: null or misaligned
+ *     pointers, n_rows < 0, H <= 0, ld* < H, a NaN slope, partial slots without ws -> GLASS_E_ARG; a header that is no plan for n_rows ->
+ *     GLASS_E_PLAN; H beyond 65535 * 64 columns -> GLASS_E_UNSUPPORTED.  n_rows == 0, or a plan without entries, returns 0
+ *     WITHOUT a launch: the results of a matrix without entries (all zero) are then the caller's to set.  The *_ws_bytes
+ *     queries: GLASS_E_PLAN for a header that is no plan, GLASS_E_ARG for H <= 0 (or n_rows < 0). */
+int64_t glass_spmm_gatv2_score_ws_bytes(const int32_t* plan_header_host, int64_t H);
+int glass_spmm_gatv2_score_f32(const int32_t* rowptr, const int32_t* col, const float* val, /* CSR of A, device */
+                               const float* X, int64_t ldx, const float* att, float slope,
+                               float* s,                                                     /* [nnz] */
+                               int64_t n_rows, int64_t H,
+                               const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_spmm_gatv2_ws_bytes(const int32_t* plan_header_host, int64_t H);
+int glass_spmm_gatv2_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val,   /* CSR of A */
+                             const float* X, int64_t ldx, const float* s,
+                             float* Y, int64_t ldy, float* L,                                /* [n_rows, H], [n_rows] */
+                             int64_t n_rows, int64_t H,
+                             const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_spmm_gatv2_edge_ws_bytes(const int32_t* plan_header_host, int64_t H);
+int glass_spmm_gatv2_edge_f32(const int32_t* rowptr, const int32_t* col, const float* val,  /* CSR of A */
+                              const float* X, int64_t ldx, const float* att, float slope, const float* s,
+                              const float* dY, int64_t lddy, const float* Y, int64_t ldy, const float* L,
+                              float* g, float* p, float* Gd, float* R,                       /* [nnz] x 2, [n_rows, H] x 2 */
+                              int64_t n_rows, int64_t H,
+                              const int32_t* plan_header_host, const int32_t* plan_dev, void* ws, void* stream);
+int64_t glass_spmm_gatv2_bwd_ws_bytes(const int32_t* plan_t_header_host, int64_t H);
+int glass_spmm_gatv2_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* val_t, const int32_t* eid_t, /* CSR of A^T */
+                             const float* X, int64_t ldx, const float* att, float slope,
+                             const float* dY, int64_t lddy, const float* p, const float* g, const float* Gd,
+                             float* dX, int64_t lddx,                                        /* [n_rows, H] */
+                             int64_t n_rows, int64_t H,
+                             const int32_t* plan_t_header_host, const int32_t* plan_t_dev, void* ws, void* stream);
+int64_t glass_spmm_gatv2_datt_ws_bytes(int64_t n_rows, int64_t H);
+int glass_spmm_gatv2_datt_f32(const float* R, float* datt,                                  /* [n_rows, H], [H] */
+                              int64_t n_rows, int64_t H, void* ws, void* stream);
+
 /* K2  normalised edge values of buildAdj (impl/models.py:83-111) on an (row,col)-sorted COO:
  *     deg = segment-sum of w per row, deg<0.5 -> +1; aggr 0=mean w/deg[row], 1=sum w,
  *     2=gcn deg[row]^-1/2 * w * deg[col]^-1/2.  Duplicate (row,col) entries stay separate CSR
